@@ -22,8 +22,14 @@ environment the script re-executes itself under `python -m torch.distributed.run
 else (RANK / WORLD_SIZE set) it just takes its rank.
 
 Prints ONE JSON line (rank 0).  `value` = whole-job tokens/s = S*steps/time.
-At N=1 the line also carries `roofline`, `cpu_baseline` and secondary legs that are never
-part of `value`: vqgan, packed, model_slice, config0_fp32, decode, generate, ring8_compute_model, elementwise.
+At N=1 the line also carries `kernels` and `roofline` (HIP events of the timed steps).  With --full it
+also carries `cpu_baseline` and secondary legs that are never part of `value`: vqgan, packed,
+model_slice, config0_fp32, decode, generate, ring8_compute_model, elementwise; at N>1, --full adds
+exchange, configs2, configs3 / configs4 and transport_trials.  A plain run does only the timed steps.
+
+--dump-outputs DIR writes what the last timed step computed (the last layer's out, lse, dq, dk, dv)
+as DIR/<name>.npy in float32, each at the same fixed, seeded sample of (token, head) rows (about
+32 MiB in all).  The inputs are seeded, so two builds compare output for output.
 """
 import argparse
 import json
@@ -931,6 +937,34 @@ class KernelTimer:
         return out
 
 
+DUMP_ROWS = 16384      # (token, head) rows sampled from each (B, c, H, D) output: 8 MiB of float32 per array at D = 128
+
+
+def dump_outputs(torch, dirname, outs, rank, world):
+    """--dump-outputs: the last layer of the last timed step -> dirname/<name>.npy, float32.  out, dq, dk and dv as the same
+    fixed, seeded sample of their (token, head) rows, in ascending row order; lse at those same (token, head) rows."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    out, lse, (dq, dk, dv) = outs
+    sfx = f"_rank{rank}" if world > 1 else ""
+    B, c, H, D = out.shape
+    n_rows = B * c * H
+    rng = np.random.default_rng(0)
+    pick = torch.from_numpy(np.sort(rng.choice(n_rows, min(n_rows, DUMP_ROWS // world), replace=False))).to(out.device)
+    for name, t in (("out", out), ("dq", dq), ("dk", dk), ("dv", dv)):
+        rows = t.reshape(n_rows, D).index_select(0, pick)
+        np.save(os.path.join(dirname, f"{name}{sfx}.npy"), rows.float().cpu().numpy())
+    if isinstance(lse, (list, tuple)):      # one (B, H, len) piece per query segment of the shard, in row order
+        lse = torch.cat(list(lse), dim=-1) if all(l.dim() == 3 for l in lse) else torch.cat([l.reshape(-1) for l in lse])
+    if lse.numel() == n_rows:               # (B, H, c) -> the (token, head) rows picked above
+        lse = lse.reshape(B, H, c).transpose(1, 2).reshape(n_rows).index_select(0, pick)
+    else:                                   # an opaque residual: a seeded sample of its own, as large as the row sample
+        lse = lse.reshape(-1)
+        lse = lse.index_select(0, torch.from_numpy(np.sort(rng.choice(lse.numel(), min(lse.numel(), DUMP_ROWS // world),
+                                                                      replace=False))).to(lse.device))
+    np.save(os.path.join(dirname, f"lse{sfx}.npy"), lse.float().cpu().numpy())
+
+
 def _free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as sck:
@@ -1054,6 +1088,12 @@ def main():
                     help="N > 1: skip the last secondary leg (a few layers under every transport / schedule pair of the C driver)")
     ap.add_argument("--no-configs34", action="store_true",
                     help="N > 1: skip the S = 262144 (BASELINE configs[3]) and packed S = 1048576 (configs[4]) legs of the line")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the timed steps: CPU baseline and secondary legs at N = 1; exchange, "
+                         "configs2 / configs3 / configs4 and transport trials at N > 1 (the --no-* options trim them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (out, lse, dq, dk, dv of its last layer) as DIR/<name>.npy, "
+                         "float32; at N > 1 every rank writes its shard as <name>_rank<r>.npy")
     args = ap.parse_args()
 
     under_launcher = "RANK" in os.environ and "WORLD_SIZE" in os.environ
@@ -1218,19 +1258,24 @@ def main():
                 c_ring.close()
             c_ring = None
 
-    def step(ring=None, ten=None, lay=None, seg=None, layers=None):
+    def step(ring=None, ten=None, lay=None, seg=None, layers=None, keep=False):
+        """keep: return the last layer's (out, lse, (dq, dk, dv)); every other layer's results are dropped at once"""
         ring = c_ring if ring is None else ring
         q_, k_, v_, do_ = (q, k, v, do) if ten is None else ten
         lay = layout if lay is None else lay
         seg = segment_ids if ten is None else seg
-        for _ in range(args.layers if layers is None else layers):
+        n_l = args.layers if layers is None else layers
+        for li in range(n_l):
             if ring is not None:
                 tab = lay if lay.kind == "table" else None      # (an ownership table travels with the call)
                 o_, l_ = ring.forward(q_, k_, v_, causal=True, segment_ids=seg, layout=tab)
-                ring.backward(q_, k_, v_, o_, l_, do_, causal=True, segment_ids=seg, layout=tab)
-                continue
-            out, lses = ring_forward(TimedOps, comm, q_, k_, v_, layout=lay, causal=True, segment_ids=seg)
-            ring_backward(TimedOps, comm, q_, k_, v_, out, lses, do_, layout=lay, causal=True, segment_ids=seg)
+                grads = ring.backward(q_, k_, v_, o_, l_, do_, causal=True, segment_ids=seg, layout=tab)
+            else:
+                o_, l_ = ring_forward(TimedOps, comm, q_, k_, v_, layout=lay, causal=True, segment_ids=seg)
+                grads = ring_backward(TimedOps, comm, q_, k_, v_, o_, l_, do_, layout=lay, causal=True, segment_ids=seg)
+            if keep and li == n_l - 1:
+                return o_, l_, grads
+            grads = None
 
     def null_ring(schedule=None):
         """the same C driver with a transport that moves nothing (buffers left as allocated): what the step costs when
@@ -1272,12 +1317,16 @@ def main():
     barrier()
     timer.enabled = world == 1
     sent_before = c_ring.bytes_sent if c_ring is not None else 0
+    last = None
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    for i in range(args.steps):
+        last = step(keep=i == args.steps - 1)
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0)
     dog.disarm()
+    if args.dump_outputs and last is not None:
+        dump_outputs(torch, args.dump_outputs, last, rank, world)
+    last = None
     sent_timed = (c_ring.bytes_sent - sent_before) if c_ring is not None else 0
     exchange = configs2 = configs3 = configs4 = transport_trials = None
 
@@ -1338,7 +1387,7 @@ def main():
 
 
     exchange = None
-    if world > 1:
+    if world > 1 and args.full:
         try:
             # the same launches with the exchange removed (buffers left as allocated): what the step
             # would cost if every transfer were free.  exposed = what the xGMI traffic adds on top.
@@ -1401,7 +1450,7 @@ def main():
             exchange = dict(exchange or {}, error=repr(e))
 
     configs2 = None
-    if world > 1 and not args.no_configs2 and S != S2 and not args.packed:
+    if world > 1 and args.full and not args.no_configs2 and S != S2 and not args.packed:
         # BASELINE configs[2] (S = 131072 over the ring) at THIS N, in the same line: `value` stays the S = 32768 strong-scaling
         # series, this object is the configuration the metric names.
         err2, ten2 = None, None
@@ -1416,7 +1465,7 @@ def main():
         if not all_ranks_ok(err2 is None):
             ten2 = None
             configs2 = {"error": err2 or "the set-up failed on another rank", "skipped_on_every_rank": True}
-    if world > 1 and not args.no_configs2 and S != S2 and not args.packed and configs2 is None:
+    if world > 1 and args.full and not args.no_configs2 and S != S2 and not args.packed and configs2 is None:
         try:
             sent0 = c_ring.bytes_sent if c_ring is not None else None
             step(ten=ten2, lay=lay2)
@@ -1531,13 +1580,13 @@ def main():
             return {"error": repr(e)[:500]}
 
     configs3 = configs4 = None
-    if world > 1 and not args.no_configs34 and not args.packed and (not shared or args.force_configs34):
+    if world > 1 and args.full and not args.no_configs34 and not args.packed and (not shared or args.force_configs34):
         torch.cuda.empty_cache()
         configs3 = other_config("configs[3] sequence (262144 tokens; its VQGAN tokenisation is the `vqgan` leg of the N = 1 line)", 262144, 2, False)
         torch.cuda.empty_cache()
         configs4 = other_config("configs[4]", 1 << 20, 2, True)
 
-    if world > 1 and c_ring is not None and not args.no_transport_trials and not args.packed:
+    if world > 1 and args.full and c_ring is not None and not args.no_transport_trials and not args.packed:
         # LAST of the secondary legs (a hang here costs only this object: the late watchdog prints the line as it stands):
         # the same few layers under EVERY (transport, schedule) pair the C driver has -- RCCL send/recv kernels or the CU-free
         # IPC transport, the direct schedule or the neighbour ring -- against the same launches with a transport that moves
@@ -1642,9 +1691,9 @@ def main():
                     torch.cuda.empty_cache()
                     return {"error": repr(e)[:500]}
 
-            if not args.no_cpu_baseline:
+            if args.full and not args.no_cpu_baseline:
                 res["cpu_baseline"] = leg(cpu_baseline, S)
-            if not args.no_vqgan:
+            if args.full and not args.no_vqgan:
                 res["vqgan"] = leg(vqgan_leg, torch)
                 res["packed"] = leg(packed_leg, torch)
                 res["model_slice"] = leg(model_slice_leg, torch)

@@ -21,7 +21,7 @@ if [[ " $STEPS " == *" smoke "* ]]; then
 fi
 if [[ " $STEPS " == *" bench "* ]]; then
   s=$(date +%s)
-  timeout 900 python bench.py --gpus 1 --steps ${BENCH_STEPS:-20} --warmup ${BENCH_WARMUP:-5} > $O/bench.json 2> $O/bench.err
+  timeout 900 python bench.py --full --gpus 1 --steps ${BENCH_STEPS:-20} --warmup ${BENCH_WARMUP:-5} > $O/bench.json 2> $O/bench.err
   echo "bench wall seconds: $(( $(date +%s) - s ))" | tee -a $O/bench.err
   python - $O/bench.json <<'PY'
 import json, sys

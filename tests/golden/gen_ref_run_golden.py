@@ -72,8 +72,8 @@ which branch runs when and what it hands the op, residual structure, module wiri
 layouts, flag names and defaults.
 
 Writes tests/golden/ref_run.npz.  Needs /root/reference (this container only); the tests read the .npz.
-Re-run:  python tests/golden/gen_ref_run_golden.py [output.npz]   (deterministic: tests/test_golden.py regenerates and compares
-when /root/reference is present)
+Re-run:  python tests/golden/gen_ref_run_golden.py [output.npz]   (deterministic: a regenerated file equals the committed
+one array for array, floats that went through a BLAS to 1e-5 of their maximum)
 """
 import ast
 import os

@@ -1,5 +1,5 @@
 """The bench line the driver consumes: the newest committed profiles/*_bench.json (written by
-the driver's command `python bench.py --gpus 1 --steps 20 --warmup 5` on an MI355X, scripts/gpu_round_check.sh) must carry every field of the
+the command `python bench.py --full --gpus 1 --steps 20 --warmup 5` on an MI355X, scripts/gpu_round_check.sh) must carry every field of the
 contract, with the metric and workload BASELINE.json names, a roofline object for the dominant kernel and a
 CPU baseline from the same run -- and bench.py must keep the command-line contract."""
 import glob
@@ -170,8 +170,43 @@ def test_bench_cli_contract_without_a_gpu():
         assert lines[-1]["rccl_ranks_seen"] is None and lines[-1]["bootstrap_backend"] == "gloo"
     h = subprocess.run([sys.executable, bench, "--help"], capture_output=True, text=True, timeout=300)
     for flag in ("--gpus", "--steps", "--warmup", "--driver", "--transport", "--schedule", "--layout", "--no-configs2",
-                 "--no-configs34", "--no-packed-1m"):
+                 "--no-configs34", "--no-packed-1m", "--full", "--dump-outputs"):
         assert flag in h.stdout
+
+
+def test_bench_dump_outputs_writes_a_fixed_float32_sample(tmp_path):
+    """--dump-outputs: out / dq / dk / dv of the last layer as the same seeded sample of their (token, head) rows, each from
+    its own tensor, lse at those same rows, all float32, the same files for the same tensors, and a size that does not grow
+    with the sequence (no GPU needed: the writer takes any torch tensors).  test_gpu_bench_dump.py checks that a run of
+    the benchmark hands it what the timed path computed."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    names = ("out", "lse", "dq", "dk", "dv")
+    for (B, c, H, D) in ((1, 4096, 32, 128), (1, 65536, 8, 8)):
+        mk = lambda: torch.randn(B, c, H, D, generator=g).to(torch.bfloat16)
+        ten = {n: mk() for n in ("out", "dq", "dk", "dv")}
+        lse = torch.randn(B, H, c, generator=g)
+        got = []
+        for run in ("a", "b"):
+            d = tmp_path / f"{c}_{run}"
+            bench.dump_outputs(torch, str(d), (ten["out"], [lse], (ten["dq"], ten["dk"], ten["dv"])), 0, 1)
+            got.append({n: np.load(d / f"{n}.npy") for n in names})
+        a, b = got
+        assert all(a[n].dtype == np.float32 and np.array_equal(a[n], b[n]) for n in names)
+        # which rows were taken: every sampled row of `out` found in `out` (random bf16 rows are distinct)
+        rows = {n: t.reshape(-1, D).float().numpy() for n, t in ten.items()}
+        where = {r.tobytes(): i for i, r in enumerate(rows["out"])}
+        pick = np.array([where[r.tobytes()] for r in a["out"]])
+        assert len(pick) == bench.DUMP_ROWS and np.all(np.diff(pick) > 0)          # distinct rows, ascending
+        for n in ("out", "dq", "dk", "dv"):
+            assert a[n].shape == (bench.DUMP_ROWS, D) and np.array_equal(a[n], rows[n][pick]), n
+        assert np.array_equal(a["lse"], lse.transpose(1, 2).reshape(-1).numpy()[pick])   # row = (token, head)
+        d = tmp_path / f"{c}_a"
+        assert os.path.getsize(d / "lse.npy") < 4 * bench.DUMP_ROWS + 1024
+        assert sum(os.path.getsize(d / f"{n}.npy") for n in names) <= 64 << 20
 
 
 def test_bench_watchdog_turns_a_hang_into_an_error_line():

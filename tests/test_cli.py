@@ -50,13 +50,24 @@ SAMPLE_VIDEO = [  # scripts/run_sample_video.sh:15-33 (run_sample_image.sh is th
     "--load_checkpoint=params::/ckpt/params", "--tokenizer=LargeWorldModel/LWM-Text-1M"]
 
 
-def _script_flags(name):
-    """Flag NAMES the reference's launch script passes (read from /root/reference when it is there)."""
-    import re
-    path = os.path.join("/root/reference/scripts", name)
-    if not os.path.exists(path):
-        return None
-    return set(re.findall(r"^\s+--([A-Za-z_.]+)=", open(path).read(), flags=re.M))
+RESTATED = {  # the command lines above -> the reference entry point whose flags they pass
+    "TRAIN_TEXT": (TRAIN_TEXT, "train"), "TRAIN_VISION": (TRAIN_VISION, "train"),
+    "VISION_CHAT": (VISION_CHAT, "vision_chat"), "SAMPLE_VIDEO": (SAMPLE_VIDEO, "vision_generation")}
+
+
+def _line_flags(line):
+    """Flag NAMES of a restated command line."""
+    return {a[2:].split("=", 1)[0] for a in line}
+
+
+def _reference_flags(entry):
+    """Names of the flags and flag groups the reference's entry point defines: its define_flags_with_default statements
+    executed with a recorder (tests/golden/gen_ref_run_golden.py -> ref_run.npz, `flags_json`).  absl refuses any other
+    name, so every flag a reference launch script passes is one of these (or a member of one of these groups)."""
+    import json
+    import numpy as np
+    with np.load(os.path.join(ROOT, "tests", "golden", "ref_run.npz")) as z:
+        return set(json.loads(str(z["flags_json"]))[entry]["flags"])
 
 
 def test_every_flag_of_the_reference_scripts_parses():
@@ -89,15 +100,18 @@ def test_every_flag_of_the_reference_scripts_parses():
     assert F.n_frames == 8 and F.top_k_video == 1000 and F.cfg_scale_image == 5.0 and F.output_file == "fireworks.mp4"
     assert build_config(F, vision=True).sample_mode == "vision"
 
-    # the flag NAMES of the scripts themselves (when the reference tree is at hand) are all known
-    for script, mod in (("run_train_text.sh", train), ("run_train_vision_text.sh", train),
-                        ("run_vision_chat.sh", vision_chat), ("run_sample_image.sh", vision_generation),
-                        ("run_sample_video.sh", vision_generation)):
-        names = _script_flags(script)
-        if names is None:
-            continue
-        for n in names:
-            assert n in mod.DEFAULTS or n.split(".")[0] in mod.GROUPS, (script, n)
+    # the flag NAMES: every one the restated lines pass is a flag (or a member of a group) of the reference's own entry
+    # point as recorded from its code -- a source independent of lwm_amd.cli -- and is known here.  Together with
+    # tests/test_golden.py::test_entry_point_flags_are_the_reference_run_definitions (the recorded flags and groups ARE
+    # lwm_amd.cli's) this covers every name any reference launch script can pass.
+    mods = {"train": train, "vision_chat": vision_chat, "vision_generation": vision_generation}
+    for tag, (line, entry) in RESTATED.items():
+        ref, mod = _reference_flags(entry), mods[entry]
+        assert ref
+        for n in _line_flags(line):
+            assert n.split(".")[0] in ref, (tag, n)
+            assert n in mod.DEFAULTS or n.split(".")[0] in mod.GROUPS, (tag, n)
+            assert (n in ref) == (n in mod.DEFAULTS), (tag, n)        # a scalar there is a scalar here
 
     with pytest.raises(SystemExit):
         parse(train.DEFAULTS, train.GROUPS, ["--no_such_flag=1"], "train")
