@@ -453,6 +453,45 @@ int lwm_gemv_fused_bf16(const LwmGemvArgs* args, void* stream);
 int lwm_softmax_ce_bf16(const void* logits, const int32_t* target, const float* weight, float* nll,
                         int32_t* correct, void* dlogits, int64_t rows, int32_t V, void* stream);
 
+/* ------------------------------------------------------------------ token sampler (lwm_version() >= 510)
+ * One decode step's choice of the next token, per output row b (lwm/vision_llama.py:476-560 _sample_vision;
+ * lwm/vision_chat.py:201-213 generate(do_sample=True)), in one launch:
+ *   logit   cfg_scale == NULL: row b of `logits`; else rows [0,B) are conditional, [B,2B) unconditional (rows = 2B) and
+ *           the logit is u + s*(c - u) with s = cfg_scale[b], three f32 roundings (no fused multiply-add);
+ *   greedy  temperature == 0: argmax, lowest index on ties;
+ *   filter  0 < top_k < V: keep every entry >= the top_k-th largest of logit / temperature (ties at it all stay);
+ *   draw    argmax over the kept entries of logit / temperature + g_j, lowest index on ties (Gumbel-max), with
+ *           g = -log(-log(u)), u = ((x >> 9) + 0.5) * 2^-23 and x word (j % 4) of Philox4x32-10 (key = seed, counter =
+ *           (j / 4, b, step, 0));
+ *   step    *step_dev - step_base (DEVICE int32: a captured graph draws new numbers on every replay), or `step` when
+ *           step_dev is NULL;
+ *   force   force_period > 0 and (step + 1) % force_period == 0: the token is force_token (lwm/vision_llama.py:549-552);
+ *   done    done != NULL (u8 [B]): a row whose done[b] is set emits pad; then done[b] |= (token == eos) (eos < 0: none);
+ *   outputs tokens[c*B + b] for c < copies (int64: the next step's input ids, both CFG halves with copies = 2) and / or
+ *           seq[b*seq_ld + step] when 0 <= step < seq_cols (int64).
+ * The token depends on (logits, cfg, temperature, top_k, seed, b, step) only.  Any V in [1, 2^30]; logits rows ld >= V
+ * apart (elements); pointers 4-byte (logits, cfg_scale, step_dev) / 8-byte (tokens, seq) aligned. */
+typedef struct LwmSampleArgs {
+    const float* logits;       /* [rows][ld] f32 */
+    int64_t ld;
+    int32_t rows, V;
+    const float* cfg_scale;    /* [rows / 2] f32 or NULL */
+    float temperature;
+    int32_t top_k;
+    uint64_t seed;
+    const int32_t* step_dev;   /* or NULL */
+    int32_t step_base, step;
+    int32_t force_period, force_token;
+    uint8_t* done;             /* [B] or NULL */
+    int64_t eos, pad;
+    int64_t* tokens;           /* [copies][B] or NULL */
+    int32_t copies;
+    int64_t* seq;              /* [B][seq_ld] or NULL */
+    int64_t seq_ld;
+    int32_t seq_cols;
+} LwmSampleArgs;
+int lwm_sample_tokens(const LwmSampleArgs* args, void* stream);
+
 /* ------------------------------------------------------------------ VQGAN
  * Primitives of the video tokeniser, lwm/vqgan.py.  All tensors are f32, NHWC,
  * dense; results are bit-exact with oracle/vqgan_ref.c (exact-f32 MFMA, fixed
@@ -502,7 +541,8 @@ int lwm_vq_gather_f32(const float* codebook, const int32_t* idx, const float* z,
 
 const char* lwm_last_error(void);
 int lwm_version(void);
-/* sizeof(LwmAttnArgs) (which = 0) / sizeof(LwmConvArgs) (1) / sizeof(LwmRingArgs) (2) as compiled into the library:
+/* sizeof(LwmAttnArgs) (which = 0) / sizeof(LwmConvArgs) (1) / sizeof(LwmRingArgs) (2) / sizeof(LwmGemvArgs) (3) /
+ * sizeof(LwmSampleArgs) (4) as compiled into the library:
  * lets a foreign-language binding verify its struct mirror at load time. */
 int lwm_sizeof(int which);
 

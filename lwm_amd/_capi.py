@@ -85,6 +85,17 @@ class LwmGemvArgs(C.Structure):
     ]
 
 
+class LwmSampleArgs(C.Structure):
+    _fields_ = [
+        ("logits", C.c_void_p), ("ld", C.c_int64), ("rows", C.c_int32), ("V", C.c_int32),
+        ("cfg_scale", C.c_void_p), ("temperature", C.c_float), ("top_k", C.c_int32), ("seed", C.c_uint64),
+        ("step_dev", C.c_void_p), ("step_base", C.c_int32), ("step", C.c_int32),
+        ("force_period", C.c_int32), ("force_token", C.c_int32), ("done", C.c_void_p), ("eos", C.c_int64),
+        ("pad", C.c_int64), ("tokens", C.c_void_p), ("copies", C.c_int32), ("seq", C.c_void_p), ("seq_ld", C.c_int64),
+        ("seq_cols", C.c_int32),
+    ]
+
+
 RING_GROUP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
 RING_SEND_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p)
 
@@ -170,6 +181,7 @@ PROTOTYPES = {
                                       C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_void_p,
                                       C.c_int32, C.c_int32, C.c_void_p]),
     "lwm_gemv_fused_bf16": (C.c_int, [C.POINTER(LwmGemvArgs), C.c_void_p]),
+    "lwm_sample_tokens": (C.c_int, [C.POINTER(LwmSampleArgs), C.c_void_p]),
     "lwm_cast_f32_to_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "lwm_sum_f32_to_bf16": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "lwm_conv2d_nhwc_f32": (C.c_int, [C.POINTER(LwmConvArgs), C.c_void_p]),
@@ -192,7 +204,7 @@ def bind(lib):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
-    for which, cls in ((0, LwmAttnArgs), (1, LwmConvArgs), (2, LwmRingArgs)):
+    for which, cls in ((0, LwmAttnArgs), (1, LwmConvArgs), (2, LwmRingArgs), (4, LwmSampleArgs)):
         if lib.lwm_sizeof(which) != C.sizeof(cls):
             raise ImportError(f"{cls.__name__}: ctypes mirror is {C.sizeof(cls)} bytes, library has "
                               f"{lib.lwm_sizeof(which)} (include/lwm_hip.h and lwm_amd/_capi.py out of step)")

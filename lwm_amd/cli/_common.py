@@ -22,6 +22,20 @@ def note(msg):
     print(f"[lwm_amd.cli] {msg}", file=sys.stderr, flush=True)
 
 
+def sampler_kwargs(model, seed, generator):
+    """How the entry points draw tokens.  Default: the torch sampler driven by `generator` (eager one-token steps).
+    LWM_DECODE_GRAPH=1: every token drawn on the device from the Philox stream of --seed (lwm_amd.ops.sample_tokens),
+    the one-token step captured once in a hipGraph -- or, for a float32 model, issued eagerly (capture takes the bf16
+    decode kernels) -- and the same --seed gives the same tokens run after run."""
+    if os.environ.get("LWM_DECODE_GRAPH", "0") != "1":
+        return dict(generator=generator)
+    graph = model.dtype == torch.bfloat16
+    if not graph:
+        note("LWM_DECODE_GRAPH=1 with a float32 model: the device sampler runs eagerly (graph capture takes the bf16 "
+             "decode kernels)")
+    return dict(seed=seed, graph=graph)
+
+
 def setup_mesh(mesh_dim: str):
     """--mesh_dim (lwm/train.py:35; tux.get_jax_mesh) -> this process's place in the (dp, fsdp, tp, sp)
     mesh; binds mesh axis "sp" to its process group.  One process per GPU: under torch.distributed.run

@@ -113,7 +113,7 @@ class Sampler:
                                   max_new_tokens=max_new_tokens or self.block_size,
                                   temperature=self.F.temperature, do_sample=True,
                                   eos_token_id=self.tokenizer.eos_token_id, pad_token_id=self.tokenizer.pad_token_id or 0,
-                                  generator=self.gen)
+                                  **C.sampler_kwargs(self.model, self.F.seed, self.gen))
         texts = []
         for text in self.tokenizer.batch_decode(new.cpu().numpy(), skip_special_tokens=True):
             eos = getattr(self.tokenizer, "eos_token", None)

@@ -62,7 +62,7 @@ def main(argv=None):
             vm = torch.cat([vm, torch.ones_like(img, dtype=torch.bool)], 1)
         return model.generate_vision(ids, [cfg_scale] * len(prompts), attention_mask=att, vision_masks=vm,
                                      max_new_tokens=n_tokens, temperature=temperature, top_k=top_k,
-                                     generator=gen).cpu().numpy()
+                                     **C.sampler_kwargs(model, F.seed, gen)).cpu().numpy()
 
     def to_u8(pix):
         return ((pix.cpu().numpy() + 1) * 127.5).astype(np.uint8)

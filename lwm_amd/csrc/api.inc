@@ -3,6 +3,7 @@
 // tests/emu/lwm_emu.cpp (host emulation of the same kernels; test-only).
 // Expects: wave_ops.h, launch.h, attn_common.h, attn_fwd.h, attn_fwd64.h, attn_bwd.h, attn_bwd64.h,
 // misc_kernels.h and "lwm_hip.h" already included.
+#include "sample.h"
 
 namespace lwm {
 
@@ -613,10 +614,41 @@ int lwm_softmax_ce_bf16(const void* logits, const int32_t* target, const float* 
     return launch("softmax_ce", softmax_ce_kernel, blocks, kCeThreads, 128, stream, p);
 }
 
+int lwm_sample_tokens(const LwmSampleArgs* a, void* stream) {
+    using namespace lwm;
+    if (!a) return fail(LWM_EINVAL, "%s", "sample_tokens: args is null");
+    if (!a->logits) return fail(LWM_EINVAL, "%s", "sample_tokens: logits is null");
+    if (a->V < 1 || a->V > (1 << 30)) return fail(LWM_EINVAL, "%s: V = %ld (need 1 <= V <= 2^30)", "sample_tokens", a->V);
+    if (a->rows < 1 || a->ld < a->V) return fail(LWM_EINVAL, "%s: rows = %ld, ld = %ld (need rows >= 1, ld >= V)", "sample_tokens", a->rows, (long)a->ld);
+    if (a->top_k < 0) return fail(LWM_EINVAL, "%s: top_k = %ld < 0", "sample_tokens", a->top_k);
+    if (!(a->temperature >= 0.0f)) return fail(LWM_EINVAL, "%s", "sample_tokens: temperature must be >= 0 (0 = greedy)");
+    if (a->cfg_scale && (a->rows & 1))
+        return fail(LWM_EINVAL, "%s: rows = %ld is odd (cfg_scale: conditional rows, then as many unconditional ones)", "sample_tokens", a->rows);
+    const int32_t B = a->cfg_scale ? a->rows / 2 : a->rows;
+    if (B > 65535) return fail(LWM_EINVAL, "%s: %ld output rows (at most 65535)", "sample_tokens", B);
+    if (!a->tokens && !a->seq) return fail(LWM_EINVAL, "%s", "sample_tokens: no output (tokens and seq are both null)");
+    if (a->tokens && a->copies < 1) return fail(LWM_EINVAL, "%s: copies = %ld < 1", "sample_tokens", a->copies);
+    if (a->seq && (a->seq_cols < 0 || a->seq_ld < a->seq_cols)) return fail(LWM_EINVAL, "%s", "sample_tokens: bad seq_cols / seq_ld");
+    if (a->force_period < 0) return fail(LWM_EINVAL, "%s: force_period = %ld < 0", "sample_tokens", a->force_period);
+    const auto mis = [](const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) != 0; };
+    if (mis(a->logits, 4) || mis(a->cfg_scale, 4) || mis(a->step_dev, 4) || mis(a->tokens, 8) || mis(a->seq, 8))
+        return fail(LWM_EINVAL, "%s", "sample_tokens: misaligned pointer (logits, cfg_scale, step_dev: 4 bytes; tokens, seq: 8)");
+    SampleParams p;
+    p.logits = a->logits; p.ld = a->ld; p.V = a->V; p.B = B; p.cfg = a->cfg_scale != nullptr; p.cfg_scale = a->cfg_scale;
+    p.temperature = a->temperature; p.top_k = a->top_k;
+    p.key0 = (uint32_t)a->seed; p.key1 = (uint32_t)(a->seed >> 32);
+    p.step_dev = a->step_dev; p.step_base = a->step_base; p.step = a->step;
+    p.force_period = a->force_period; p.force_token = a->force_token;
+    p.done = a->done; p.eos = a->eos; p.pad = a->pad;
+    p.tokens = a->tokens; p.copies = a->copies;
+    p.seq = a->seq; p.seq_ld = a->seq_ld; p.seq_cols = a->seq_cols;
+    return launch("sample_tokens", sample_kernel, B, kSampleThreads, kSampleLdsBytes, stream, p);
+}
+
 const char* lwm_last_error(void) { return lwm::g_err; }
-int lwm_version(void) { return 500; }
+int lwm_version(void) { return 510; }
 int lwm_sizeof(int which) {
-    return which == 0 ? (int)sizeof(LwmAttnArgs) : which == 1 ? (int)sizeof(LwmConvArgs) : which == 2 ? (int)sizeof(LwmRingArgs) : which == 3 ? (int)sizeof(LwmGemvArgs) : -1;
+    return which == 0 ? (int)sizeof(LwmAttnArgs) : which == 1 ? (int)sizeof(LwmConvArgs) : which == 2 ? (int)sizeof(LwmRingArgs) : which == 3 ? (int)sizeof(LwmGemvArgs) : which == 4 ? (int)sizeof(LwmSampleArgs) : -1;
 }
 
 }  // extern "C"

@@ -161,6 +161,24 @@ def cached_visibility(B, Q, max_len, q0, attention_mask, device):
     return mask
 
 
+def capture_decode_step(step, device, capture=True):
+    """The scaffold of a hipGraph-captured decode loop: `step` (a one-token step whose inputs and outputs are static
+    tensors and whose cache index lives on the device) runs once eagerly on a side stream -- library handles, first-call
+    state -- and is then captured once, on one stream.  -> (the eager call's result, the graph or None, the captured
+    call's result, which every replay rewrites)."""
+    side = torch.cuda.Stream(device=device)
+    side.wait_stream(torch.cuda.current_stream(device))
+    with torch.cuda.stream(side):
+        first = step()
+    torch.cuda.current_stream(device).wait_stream(side)
+    if not capture:
+        return first, None, None
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        static = step()
+    return first, g, static
+
+
 class LLaMAAttention(torch.nn.Module):
     """FlaxLLaMAAttention.__call__, training branch (lwm/llama.py:494-570, :616-617)."""
 
@@ -454,19 +472,11 @@ class LLaMAForCausalLM(torch.nn.Module):
                 idx.add_(1)
                 return logits
 
-            # one eager step on a side stream (library handles, first-call state), then capture
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                emit(step())
-            torch.cuda.current_stream(dev).wait_stream(side)
-            if max_new_tokens > 2:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    static_logits = step()
-                for _ in range(max_new_tokens - 2):
-                    g.replay()
-                    emit(static_logits)
+            first, g, static_logits = capture_decode_step(step, dev, capture=max_new_tokens > 2)
+            emit(first)
+            for _ in range(max_new_tokens - 2):
+                g.replay()
+                emit(static_logits)
         out = torch.cat(tokens, dim=1)
         return (out, torch.stack(logits_out, 1)) if return_logits else out
 

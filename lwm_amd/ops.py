@@ -444,3 +444,47 @@ def vq_gather(codebook, idx, z=None):
                                        None if z is None else _f32c(z, "z"), out.data_ptr(),
                                        idx.numel(), E, D, _stream_ptr()), "lwm_vq_gather_f32")
     return out
+
+
+def sample_tokens(logits, *, temperature, top_k, seed, step_dev=None, step=0, step_base=0, cfg_scale=None, force_period=0,
+                  force_token=0, done=None, eos=None, pad=0, tokens_out=None, copies=1, seq_out=None):
+    """One decode step's next token per output row, drawn on the device (lwm_sample_tokens, csrc/sample.h): guidance
+    over (2B, V) logits when cfg_scale (B,) is given (conditional rows first), temperature (0 = greedy), top-k (0 =
+    none), a Gumbel-max draw from the Philox stream of (seed, entry, row, step).  `step` is read from the one-element
+    int32 device tensor step_dev (minus step_base) or taken from the host value.  force_period / force_token, done ((B,)
+    uint8) / eos / pad, the int64 outputs tokens_out ((copies * B, 1): the next step's input ids) and seq_out ((B, n):
+    column `step`) as include/lwm_hip.h documents.  Returns tokens_out -- allocated when not given; a call that is handed
+    every output allocates nothing and can be captured in a hipGraph."""
+    if not logits.is_cuda or logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("sample_tokens: logits must be a (rows, V) f32 device tensor with contiguous rows")
+    rows, V = logits.shape
+    B = rows // 2 if cfg_scale is not None else rows
+
+    def dev_ptr(t, name, dtype, n):
+        if t is None:
+            return None
+        if not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or t.numel() != n:
+            raise ValueError(f"sample_tokens: {name} must be a contiguous {dtype} device tensor of {n} elements")
+        return t.data_ptr()
+
+    if tokens_out is None:
+        tokens_out = torch.empty((copies * B, 1), dtype=torch.int64, device=logits.device)
+    a = _capi.LwmSampleArgs()
+    a.logits, a.ld, a.rows, a.V = logits.data_ptr(), logits.stride(0), rows, V
+    a.cfg_scale = dev_ptr(cfg_scale, "cfg_scale", torch.float32, B)
+    a.temperature, a.top_k = float(temperature), int(top_k or 0)
+    a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    a.step_dev = dev_ptr(step_dev, "step_dev", torch.int32, 1)
+    a.step_base, a.step = int(step_base), int(step)
+    a.force_period, a.force_token = int(force_period), int(force_token)
+    a.done = dev_ptr(done, "done", torch.uint8, B)
+    a.eos, a.pad = -1 if eos is None else int(eos), int(pad)
+    a.tokens, a.copies = dev_ptr(tokens_out, "tokens_out", torch.int64, copies * B), int(copies)
+    if seq_out is not None:
+        if not seq_out.is_cuda or seq_out.dtype != torch.int64 or seq_out.dim() != 2 or seq_out.shape[0] != B or \
+                seq_out.stride(1) != 1:
+            raise ValueError(f"sample_tokens: seq_out must be a ({B}, n) int64 device tensor with contiguous rows")
+        a.seq, a.seq_ld, a.seq_cols = seq_out.data_ptr(), seq_out.stride(0), seq_out.shape[1]
+    L = lib()
+    _capi.check(L, L.lwm_sample_tokens(C.byref(a), _stream_ptr()), "lwm_sample_tokens")
+    return tokens_out

@@ -8,8 +8,10 @@ from __future__ import annotations
 
 import torch
 
-from .llama import LLaMAConfig, LLaMAForCausalLM, _dense
+from . import ops as _ops
+from .llama import LLaMAConfig, LLaMAForCausalLM, _dense, capture_decode_step
 from .llama_ops import chunked_lm_head_loss, dense
+from .ringattention import sp_size_rank
 
 
 class VideoLLaMAConfig(LLaMAConfig):
@@ -103,22 +105,120 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
             logits = logits.masked_fill(logits < kth, float("-inf"))
         return torch.multinomial(torch.softmax(logits, -1), 1, generator=gen)
 
+    # seed-driven decoding: every token drawn on the device (ops.sample_tokens); `done` is read back this often
+    DONE_CHECK_EVERY = 16
+
+    @staticmethod
+    def _check_seed_args(seed, graph, generator):
+        if seed is not None and generator is not None:
+            raise ValueError("pass generator= (the torch sampler, eager) or seed= (the device sampler), not both")
+        if graph and seed is None:
+            raise ValueError("graph=True draws every token on the device: it needs seed= (generator= drives the eager "
+                             "torch sampler)")
+
+    def _seeded_decode(self, input_ids, vision_masks, attention_mask, max_length, max_new_tokens, head, *, seed, graph,
+                       temperature, top_k, cfg=None, force_period=0, force_token=0, eos=None, pad=0, return_logits=False):
+        """Decoding with every token chosen by ops.sample_tokens (csrc/sample.h) from the Philox stream of `seed`: the
+        sampler also writes the next step's input ids, the output column and the done flags, so no step waits for the
+        host.  graph=True: the one-token step -- layers, head, sampler, cache index -- is captured ONCE in a hipGraph
+        and replayed (the scaffold of LLaMAForCausalLM.generate(graph=True)).  `cfg` (B,) f32: a batch of B conditional
+        prompts followed by B unconditional ones.  With `eos`, `done` is read back every DONE_CHECK_EVERY tokens.
+        -> ((B, max_new_tokens) int64, logits of every step (rows, steps, V) f32 or None)."""
+        rows, S = input_ids.shape
+        B = rows // 2 if cfg is not None else rows
+        dev = input_ids.device
+        if graph:
+            if self.dtype != torch.bfloat16:
+                raise NotImplementedError("graph=True captures the bf16 decode kernels; a float32 model samples on the "
+                                          "device eagerly (graph=False)")
+            import torch.distributed as dist
+            if sp_size_rank("sp")[0] > 1 or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+                raise NotImplementedError("graph=True is single-rank (the cross-rank combine is not captured)")
+        max_length = max_length or (S + max_new_tokens)
+        h, cache, ext, pos = self._prefill(input_ids, vision_masks, attention_mask, max_length)
+        seq = torch.full((B, max_new_tokens), int(pad), dtype=torch.int64, device=dev)
+        tok = torch.empty((rows, 1), dtype=torch.int64, device=dev)
+        done = None if eos is None else torch.zeros(B, dtype=torch.uint8, device=dev)
+        kw = dict(temperature=float(temperature), top_k=int(top_k or 0), seed=int(seed), cfg_scale=cfg,
+                  force_period=force_period, force_token=force_token, done=done, eos=eos, pad=int(pad), tokens_out=tok,
+                  copies=rows // B, seq_out=seq)
+        logits_out = []
+        keep = (lambda lg: logits_out.append(lg.clone())) if return_logits else (lambda lg: None)
+        every = self.DONE_CHECK_EVERY
+        all_done = lambda i: done is not None and (i + 1) % every == 0 and bool(done.all())    # after token i
+
+        logits = dense(h, head, torch.float32)
+        keep(logits)
+        _ops.sample_tokens(logits, step=0, **kw)
+        if not graph:
+            for i in range(1, max_new_tokens):
+                if all_done(i - 1):
+                    break
+                h, pos = self._step(tok, cache, ext, pos)
+                logits = dense(h, head, torch.float32)
+                keep(logits)
+                _ops.sample_tokens(logits, step=i, **kw)
+        elif max_new_tokens > 1 and not all_done(0):
+            index = int(cache[0]["cache_index"])
+            idx = torch.tensor([index], dtype=torch.int32, device=dev)
+            ar = torch.arange(max_length, device=dev, dtype=torch.int32)
+            posd = pos.clone()
+            dcache = [dict(cached_key=c["cached_key"], cached_value=c["cached_value"], index_dev=idx) for c in cache]
+
+            def step():            # token i is sampled at cache index index + i - 1
+                mask = ((ar[None, :] <= idx) & (ext > 0))[:, None, None, :]
+                for c in dcache:
+                    c["mask_dev"] = mask
+                lg = dense(self.hidden_states(tok, None, ext, None, posd, dcache)[:, -1], head, torch.float32)
+                _ops.sample_tokens(lg, step_dev=idx, step_base=index - 1, **kw)
+                posd.add_(1)
+                idx.add_(1)
+                return lg
+
+            first, g, static_logits = capture_decode_step(step, dev, capture=max_new_tokens > 2)
+            keep(first)
+            for i in range(2, max_new_tokens):
+                if all_done(i - 1):
+                    break
+                g.replay()
+                keep(static_logits)
+        return seq, (torch.stack(logits_out, 1) if return_logits else None)
+
     @torch.no_grad()
     def generate(self, input_ids, vision_masks=None, attention_mask=None, max_new_tokens=16, max_length=None,
-                 temperature=1.0, top_k=None, do_sample=False, eos_token_id=None, pad_token_id=0, generator=None):
+                 temperature=1.0, top_k=None, do_sample=False, eos_token_id=None, pad_token_id=0, generator=None,
+                 seed=None, graph=False, return_logits=False):
         """Text continuation of a (left-padded) vision-language prompt -- what lwm/vision_chat.py:205-227
         runs with sample_mode='text': prefill over both embedding tables, then one token at a time
-        through the text head.  Returns the NEW tokens (B, max_new_tokens), pad after eos."""
+        through the text head.  Returns the NEW tokens (B, max_new_tokens), pad after eos (and the f32 logits of
+        every step, (B, steps, V), with return_logits).
+
+        Sampling: generator= (or neither generator nor seed) = the torch sampler, eager, as before; seed= = every
+        token drawn on the device by ops.sample_tokens from the Philox stream of `seed` (bf16 or float32 models);
+        seed= with graph=True = the same one-token step captured once in a hipGraph and replayed (bf16, one rank).
+        With a seed the loop reads `done` back every DONE_CHECK_EVERY tokens instead of after every token."""
         if self.cfg.sample_mode != "text":
             raise ValueError("generate() decodes text: set sample_mode='text' (scripts/run_vision_chat.sh)")
+        if seed is not None or graph:
+            self._check_seed_args(seed, graph, generator)
+            out, logits = self._seeded_decode(input_ids, vision_masks, attention_mask, max_length, max_new_tokens,
+                                              self.lm_head, seed=seed, graph=graph,
+                                              temperature=temperature if do_sample else 0.0, top_k=top_k,
+                                              eos=eos_token_id, pad=pad_token_id, return_logits=return_logits)
+            out = out.to(input_ids.dtype)
+            return (out, logits) if return_logits else out
         B, S = input_ids.shape
         max_length = max_length or (S + max_new_tokens)
         h, cache, ext, pos = self._prefill(input_ids, vision_masks, attention_mask, max_length)
         head = self.lm_head        # (f32 logits from the bf16 kernel: llama_ops.dense)
         out = torch.full((B, max_new_tokens), int(pad_token_id), dtype=input_ids.dtype, device=input_ids.device)
         done = torch.zeros(B, dtype=torch.bool, device=input_ids.device)
+        logits_out = []
         for i in range(max_new_tokens):
-            tok = self._pick(dense(h, head, torch.float32), temperature, top_k, do_sample, generator).to(input_ids.dtype)
+            logits = dense(h, head, torch.float32)
+            if return_logits:
+                logits_out.append(logits.clone())
+            tok = self._pick(logits, temperature, top_k, do_sample, generator).to(input_ids.dtype)
             out[:, i] = torch.where(done, out[:, i], tok[:, 0])
             if eos_token_id is not None:
                 done |= tok[:, 0] == eos_token_id
@@ -126,16 +226,22 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
                     break
             if i + 1 < max_new_tokens:
                 h, pos = self._step(tok, cache, ext, pos)
-        return out
+        return (out, torch.stack(logits_out, 1)) if return_logits else out
 
     @torch.no_grad()
     def generate_vision(self, input_ids, cfg_scales, attention_mask=None, vision_masks=None, max_new_tokens=257,
-                        temperature=1.0, top_k=None, generator=None, max_length=None):
+                        temperature=1.0, top_k=None, generator=None, max_length=None, seed=None, graph=False,
+                        return_logits=False):
         """FlaxVideoLLaMAForCausalLM.generate_vision / _sample_vision (lwm/vision_llama.py:476-745):
         the batch holds the conditional prompts followed by the same number of unconditional ones;
         logits = uncond + cfg * (cond - uncond) over the VISION head (sample_mode='vision'), top-k /
         temperature sampling, every 257th new token forced to the end-of-frame code 8192 (:549-552),
-        the chosen token fed to both halves.  Returns the new tokens of the conditional half."""
+        the chosen token fed to both halves.  Returns the new tokens of the conditional half (and, with return_logits,
+        the f32 logits of both halves at every step, (2B, steps, V)).
+
+        Sampling as generate(): generator= = the torch sampler, eager; seed= = ops.sample_tokens on the device, which
+        also mixes the halves, forces the end-of-frame code and feeds both halves; seed= with graph=True = that step
+        captured once in a hipGraph and replayed (bf16, one rank)."""
         if self.cfg.sample_mode != "vision":
             raise ValueError("generate_vision() needs sample_mode='vision' (scripts/run_sample_image.sh)")
         B2, S = input_ids.shape
@@ -143,12 +249,23 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
             raise ValueError("generate_vision: batch = conditional prompts + as many unconditional ones")
         B = B2 // 2
         cfg = torch.as_tensor(cfg_scales, dtype=torch.float32, device=input_ids.device).reshape(-1, 1).expand(B, 1)
+        if seed is not None or graph:
+            self._check_seed_args(seed, graph, generator)
+            out, logits = self._seeded_decode(input_ids, vision_masks, attention_mask, max_length, max_new_tokens,
+                                              self._vision_kernel().contiguous(), seed=seed, graph=graph,
+                                              temperature=temperature, top_k=top_k, cfg=cfg.reshape(B).contiguous(),
+                                              force_period=257, force_token=8192, return_logits=return_logits)
+            out = out.to(input_ids.dtype)
+            return (out, logits) if return_logits else out
         max_length = max_length or (S + max_new_tokens)
         h, cache, ext, pos = self._prefill(input_ids, vision_masks, attention_mask, max_length)
         head = self._vision_kernel().contiguous()
         out = torch.empty((B, max_new_tokens), dtype=input_ids.dtype, device=input_ids.device)
+        logits_out = []
         for i in range(max_new_tokens):
             logits = dense(h, head, torch.float32)
+            if return_logits:
+                logits_out.append(logits.clone())
             cond, uncond = logits[:B], logits[B:]
             tok = self._pick(uncond + cfg * (cond - uncond), temperature, top_k, True, generator).to(input_ids.dtype)
             if (i + 1) % 257 == 0:
@@ -156,4 +273,4 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
             out[:, i] = tok[:, 0]
             if i + 1 < max_new_tokens:
                 h, pos = self._step(torch.cat([tok, tok], 0), cache, ext, pos)
-        return out
+        return (out, torch.stack(logits_out, 1)) if return_logits else out
