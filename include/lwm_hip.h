@@ -346,6 +346,53 @@ int lwm_kv_cache_write_at(void* cache, const void* src, int32_t B, int64_t cache
                           int64_t cache_rows, int64_t src_row0, int64_t nrows, int32_t row_elems,
                           void* stream);
 
+/* ------------------------------------------------------------------ 8-bit KV cache (lwm_version() >= 520)
+ * The cache as OCP e4m3fn bytes with one f32 scale per (row, head): 0.516 of the bf16 cache's bytes, in
+ * memory and per decode step.  Per layer four tensors:
+ *   cached_key, cached_value  uint8 (B, max_length, H, 128), the bits of e4m3fn, heads of a row contiguous;
+ *   key_scale, value_scale    f32   (B, max_length, H).
+ * One head of one row (128 bf16 values x): amax = max |x|; s = the smallest power of two with
+ * amax / s <= 448, clamped to [2^-126, 2^127], s = 1 when amax == 0; q = e4m3(x / s), round to nearest even
+ * (x / s is exact and in range: nothing saturates).  q * s is exactly representable in bf16.  Non-finite
+ * inputs are not supported.
+ *
+ * lwm_kv8_cache_write / _at: the arguments of lwm_kv_cache_write / _at (row_elems = H * 128; cache strides in
+ * bytes, src strides in bf16 elements) plus the scale tensor, its batch stride in floats, and H. */
+int lwm_kv8_cache_write(void* cache, const void* src, int32_t B, int64_t cache_stride_b,
+                        int64_t src_stride_b, int64_t dst_row0, int64_t src_row0, int64_t nrows,
+                        int32_t row_elems, float* scale, int64_t scale_stride_b, int32_t H, void* stream);
+int lwm_kv8_cache_write_at(void* cache, const void* src, int32_t B, int64_t cache_stride_b,
+                           int64_t src_stride_b, const int32_t* dst_row0_dev, int64_t row_offset,
+                           int64_t cache_rows, int64_t src_row0, int64_t nrows, int32_t row_elems,
+                           float* scale, int64_t scale_stride_b, int32_t H, void* stream);
+
+/* Cached-decode attention (one query per batch row) over that cache: the contract of lwm_attn_fwd's decode
+ * case (Sq = 1, dense_mask, k_splits, final_out = 0).  The visible key range of each (B, Sk) mask row is
+ * partitioned over k_splits pieces, one workgroup each; masked keys inside it contribute nothing whatever
+ * their bytes and scales hold; the normalised partials out_acc [k_splits,B,1,H,D] f32 and lse_acc
+ * [k_splits,B,H,1] f32 are merged by lwm_attn_combine; a row with nothing visible gives (0, -inf).
+ * D = 128; q, the cache rows (k/v_stride_* in bytes) and out_acc 16-byte aligned; scale strides in floats, the
+ * H scales of a row contiguous. */
+typedef struct LwmKv8DecodeArgs {
+    LwmTensor4 q;                   /* bf16 (B,1,H,D) */
+    const void* k;                  /* e4m3 bytes (B,Sk,H,D) */
+    const void* v;
+    int64_t k_stride_b, k_stride_s, k_stride_h;
+    int64_t v_stride_b, v_stride_s, v_stride_h;
+    const float* k_scale;           /* (B,Sk,H) */
+    const float* v_scale;
+    int64_t k_scale_stride_b, k_scale_stride_s;
+    int64_t v_scale_stride_b, v_scale_stride_s;
+    const uint8_t* dense_mask;      /* (B,Sk) u8, nonzero = visible; NULL = all visible */
+    int64_t mask_stride_b;
+    int32_t B, Sk, H, D;
+    float scale;                    /* softmax scale, > 0 */           
+    int32_t k_splits;
+    float* out_acc;
+    float* lse_acc;
+} LwmKv8DecodeArgs;
+int lwm_attn_decode_kv8(const LwmKv8DecodeArgs* args, void* stream);
+
 /* Elementwise helpers of the ring driver (HBM-bound). */
 /* dst_bf16[n] = (bf16) src_f32[n] */
 int lwm_cast_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream);
@@ -542,7 +589,7 @@ int lwm_vq_gather_f32(const float* codebook, const int32_t* idx, const float* z,
 const char* lwm_last_error(void);
 int lwm_version(void);
 /* sizeof(LwmAttnArgs) (which = 0) / sizeof(LwmConvArgs) (1) / sizeof(LwmRingArgs) (2) / sizeof(LwmGemvArgs) (3) /
- * sizeof(LwmSampleArgs) (4) as compiled into the library:
+ * sizeof(LwmSampleArgs) (4) / sizeof(LwmKv8DecodeArgs) (5) as compiled into the library:
  * lets a foreign-language binding verify its struct mirror at load time. */
 int lwm_sizeof(int which);
 

@@ -26,14 +26,20 @@ def sampler_kwargs(model, seed, generator):
     """How the entry points draw tokens.  Default: the torch sampler driven by `generator` (eager one-token steps).
     LWM_DECODE_GRAPH=1: every token drawn on the device from the Philox stream of --seed (lwm_amd.ops.sample_tokens),
     the one-token step captured once in a hipGraph -- or, for a float32 model, issued eagerly (capture takes the bf16
-    decode kernels) -- and the same --seed gives the same tokens run after run."""
+    decode kernels) -- and the same --seed gives the same tokens run after run.
+    LWM_KV_CACHE=fp8: the 8-bit KV cache (generate(kv_dtype="fp8"): half the cache bytes, held and read per token;
+    bf16 models on one rank), with either sampler."""
+    kv = os.environ.get("LWM_KV_CACHE", "").lower()
+    if kv not in ("", "bf16", "fp8"):
+        raise SystemExit(f"LWM_KV_CACHE={kv!r}: 'fp8', 'bf16' (the default) or unset")
+    extra = dict(kv_dtype="fp8") if kv == "fp8" else {}
     if os.environ.get("LWM_DECODE_GRAPH", "0") != "1":
-        return dict(generator=generator)
+        return dict(generator=generator, **extra)
     graph = model.dtype == torch.bfloat16
     if not graph:
         note("LWM_DECODE_GRAPH=1 with a float32 model: the device sampler runs eagerly (graph capture takes the bf16 "
              "decode kernels)")
-    return dict(seed=seed, graph=graph)
+    return dict(seed=seed, graph=graph, **extra)
 
 
 def setup_mesh(mesh_dim: str):

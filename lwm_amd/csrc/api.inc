@@ -4,6 +4,7 @@
 // Expects: wave_ops.h, launch.h, attn_common.h, attn_fwd.h, attn_fwd64.h, attn_bwd.h, attn_bwd64.h,
 // misc_kernels.h and "lwm_hip.h" already included.
 #include "sample.h"
+#include "attn_decode_kv8.h"
 
 namespace lwm {
 
@@ -196,6 +197,92 @@ int lwm_kv_cache_write_at(void* cache, const void* src, int32_t B, int64_t cache
     return launch("kv_cache_write_at", kv_cache_write_at_kernel, blocks, 256, 0, stream, (bf16_t*)cache,
                   (const bf16_t*)src, (int)B, cache_stride_b, src_stride_b, dst_row0_dev, row_offset,
                   cache_rows, src_row0, nrows, (int)row_elems);
+}
+
+static int kv8_write_params(const char* name, lwm::Kv8WriteParams* p, void* cache, const void* src, int32_t B,
+                            int64_t cache_stride_b, int64_t src_stride_b, int64_t src_row0, int64_t nrows,
+                            int32_t row_elems, float* scale, int64_t scale_stride_b, int32_t H) {
+    using namespace lwm;
+    if (!cache || !src || !scale) return fail(LWM_EINVAL, "%s: null pointer", name);
+    if (B < 0 || nrows < 0 || H <= 0 || src_row0 < 0 || cache_stride_b < 0 || scale_stride_b < 0 || src_stride_b < 0)
+        return fail(LWM_EINVAL, "%s: bad dimension", name);
+    if (row_elems != H * kHeadDim)
+        return fail(LWM_EUNSUPPORTED, "%s: row_elems = %ld, H * 128 = %ld (head_dim is 128)", name, (long)row_elems, (long)H * kHeadDim);
+    if (!aligned16(cache) || !aligned16(src) || (cache_stride_b & 15) || (src_stride_b & 7) || (((uintptr_t)scale) & 3))
+        return fail(LWM_EUNSUPPORTED, "%s: misaligned (cache and src rows 16-byte aligned, scale 4-byte)", name);
+    p->cache = (uint8_t*)cache; p->scale = scale; p->src = (const bf16_t*)src;
+    p->cache_sb = cache_stride_b; p->scale_sb = scale_stride_b; p->src_sb = src_stride_b;
+    p->row0_dev = nullptr; p->dst_row0 = 0; p->cache_rows = 0;
+    p->src_row0 = src_row0; p->nrows = nrows; p->B = B; p->H = H;
+    return 0;
+}
+
+static long kv8_write_blocks(const lwm::Kv8WriteParams& p) {
+    const int64_t blocks = ((int64_t)p.B * p.nrows * p.H * 16 + 255) / 256;
+    return (long)(blocks > 16384 ? 16384 : blocks);
+}
+
+int lwm_kv8_cache_write(void* cache, const void* src, int32_t B, int64_t cache_stride_b,
+                        int64_t src_stride_b, int64_t dst_row0, int64_t src_row0, int64_t nrows,
+                        int32_t row_elems, float* scale, int64_t scale_stride_b, int32_t H, void* stream) {
+    using namespace lwm;
+    Kv8WriteParams p;
+    int r;
+    if ((r = kv8_write_params("kv8_cache_write", &p, cache, src, B, cache_stride_b, src_stride_b, src_row0, nrows,
+                              row_elems, scale, scale_stride_b, H))) return r;
+    if (dst_row0 < 0) return fail(LWM_EINVAL, "%s", "kv8_cache_write: bad dimension");
+    if (B == 0 || nrows == 0) return LWM_OK;
+    p.dst_row0 = dst_row0;
+    p.cache_rows = dst_row0 + nrows;              // the caller has checked the range against its cache
+    return launch("kv8_quant_write", kv8_quant_write_kernel, kv8_write_blocks(p), 256, 0, stream, p);
+}
+
+int lwm_kv8_cache_write_at(void* cache, const void* src, int32_t B, int64_t cache_stride_b,
+                           int64_t src_stride_b, const int32_t* dst_row0_dev, int64_t row_offset,
+                           int64_t cache_rows, int64_t src_row0, int64_t nrows, int32_t row_elems,
+                           float* scale, int64_t scale_stride_b, int32_t H, void* stream) {
+    using namespace lwm;
+    Kv8WriteParams p;
+    int r;
+    if ((r = kv8_write_params("kv8_cache_write_at", &p, cache, src, B, cache_stride_b, src_stride_b, src_row0, nrows,
+                              row_elems, scale, scale_stride_b, H))) return r;
+    if (!dst_row0_dev) return fail(LWM_EINVAL, "%s", "kv8_cache_write_at: null pointer");
+    if (cache_rows < 0) return fail(LWM_EINVAL, "%s", "kv8_cache_write_at: bad dimension");
+    if (B == 0 || nrows == 0) return LWM_OK;
+    p.row0_dev = dst_row0_dev;
+    p.dst_row0 = row_offset;
+    p.cache_rows = cache_rows;
+    return launch("kv8_quant_write_at", kv8_quant_write_at_kernel, kv8_write_blocks(p), 256, 0, stream, p);
+}
+
+int lwm_attn_decode_kv8(const LwmKv8DecodeArgs* a, void* stream) {
+    using namespace lwm;
+    if (!a) return fail(LWM_EINVAL, "%s", "attn_decode_kv8: args is null");
+    int r;
+    if ((r = check_t4("q", a->q, true))) return r;
+    if (a->D != kHeadDim) return fail(LWM_EUNSUPPORTED, "%s: head_dim %ld (only 128)", "attn_decode_kv8", a->D);
+    if (a->B < 0 || a->Sk < 0 || a->H <= 0) return fail(LWM_EINVAL, "%s", "attn_decode_kv8: bad dimension");
+    if (!(a->scale > 0.0f)) return fail(LWM_EINVAL, "%s", "attn_decode_kv8: scale must be > 0");
+    if (!a->k || !a->v || !a->k_scale || !a->v_scale || !a->out_acc || !a->lse_acc)
+        return fail(LWM_EINVAL, "%s", "attn_decode_kv8: null pointer (k, v, k_scale, v_scale, out_acc, lse_acc)");
+    if (!aligned16(a->k) || !aligned16(a->v) || !aligned16(a->out_acc) || ((a->k_stride_b | a->k_stride_s | a->k_stride_h |
+                                                                          a->v_stride_b | a->v_stride_s | a->v_stride_h) & 15))
+        return fail(LWM_EUNSUPPORTED, "%s", "attn_decode_kv8: cache rows and out_acc must be 16-byte aligned (pointers and strides)");
+    if ((((uintptr_t)a->k_scale | (uintptr_t)a->v_scale | (uintptr_t)a->lse_acc) & 3))
+        return fail(LWM_EUNSUPPORTED, "%s", "attn_decode_kv8: scales and lse_acc must be 4-byte aligned");
+    if (a->k_splits < 0 || a->k_splits > 4096) return fail(LWM_EINVAL, "%s", "attn_decode_kv8: k_splits out of range");
+    if (a->B == 0) return LWM_OK;
+    Kv8DecodeParams p;
+    p.q = (const bf16_t*)a->q.ptr; p.q_sb = a->q.stride_b; p.q_sh = a->q.stride_h;
+    p.k = (const uint8_t*)a->k; p.v = (const uint8_t*)a->v; p.k_scale = a->k_scale; p.v_scale = a->v_scale;
+    p.k_sb = a->k_stride_b; p.k_ss = a->k_stride_s; p.k_sh = a->k_stride_h;
+    p.v_sb = a->v_stride_b; p.v_ss = a->v_stride_s; p.v_sh = a->v_stride_h;
+    p.ks_sb = a->k_scale_stride_b; p.ks_ss = a->k_scale_stride_s;
+    p.vs_sb = a->v_scale_stride_b; p.vs_ss = a->v_scale_stride_s;
+    p.dense_mask = a->dense_mask; p.msk_sb = a->mask_stride_b;
+    p.B = a->B; p.Sk = a->Sk; p.H = a->H; p.k_splits = a->k_splits > 1 ? a->k_splits : 1;
+    p.scale = a->scale; p.out_acc = a->out_acc; p.lse_acc = a->lse_acc;
+    return launch("attn_decode_kv8", attn_decode_kv8_kernel, (long)p.B * p.k_splits, kDecThreads, kDec8LdsBytes, stream, p);
 }
 
 static int check_bwd(const LwmAttnArgs* a) {
@@ -646,9 +733,9 @@ int lwm_sample_tokens(const LwmSampleArgs* a, void* stream) {
 }
 
 const char* lwm_last_error(void) { return lwm::g_err; }
-int lwm_version(void) { return 510; }
+int lwm_version(void) { return 520; }
 int lwm_sizeof(int which) {
-    return which == 0 ? (int)sizeof(LwmAttnArgs) : which == 1 ? (int)sizeof(LwmConvArgs) : which == 2 ? (int)sizeof(LwmRingArgs) : which == 3 ? (int)sizeof(LwmGemvArgs) : which == 4 ? (int)sizeof(LwmSampleArgs) : -1;
+    return which == 0 ? (int)sizeof(LwmAttnArgs) : which == 1 ? (int)sizeof(LwmConvArgs) : which == 2 ? (int)sizeof(LwmRingArgs) : which == 3 ? (int)sizeof(LwmGemvArgs) : which == 4 ? (int)sizeof(LwmSampleArgs) : which == 5 ? (int)sizeof(LwmKv8DecodeArgs) : -1;
 }
 
 }  // extern "C"

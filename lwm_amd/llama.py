@@ -238,6 +238,8 @@ class LLaMAAttention(torch.nn.Module):
         cache_index int); `attention_mask`: (B, max_length), ones beyond the prompt (:1121-1124)."""
         B, Q = xq.shape[:2]
         ck, cv = cache["cached_key"], cache["cached_value"]
+        if "key_scale" in cache:
+            return self._cached_kv8(xq, xk, xv, attention_mask, cache)
         if "index_dev" in cache:
             # hipGraph-capturable decode step: cache_index lives on the device (one int32 shared by all
             # layers), the mask was built from it once for this step, and the new row is written by
@@ -266,6 +268,49 @@ class LLaMAAttention(torch.nn.Module):
         mask = cached_visibility(B, Q, max_len, q0, attention_mask, xq.device)
         cache["cache_index"] = concatenate_to_cache(ck, cv, xk.contiguous(), xv, idx, axis_name="sp")
         return ringattention_inference(xq.contiguous(), ck, cv, mask, axis_name="sp")
+
+    def _cached_kv8(self, xq, xk, xv, attention_mask, cache):
+        """_cached over an 8-bit cache (init_cache(kv_dtype="fp8"): e4m3 bytes + one scale per row and head,
+        csrc/attn_decode_kv8.h).  Prefill (cache_index == 0): the cached path attends over rows [0, Q) only -- rows past
+        Q are invisible -- so the block attends over its OWN bf16 keys and values under the same structured mask, and
+        the rows are quantised into the cache afterwards: the prompt's own attention sees unquantised keys.  A decode
+        step quantises its row, then streams the cache (lwm_attn_decode_kv8 + the split-K combine)."""
+        from .ring import _pick_splits
+        B, Q, H, D = xq.shape
+        ck, cv, ks, vs = cache["cached_key"], cache["cached_value"], cache["key_scale"], cache["value_scale"]
+        if xq.dtype != torch.bfloat16:
+            raise NotImplementedError("kv_dtype='fp8' with a float32 model: the 8-bit cache quantises bf16 rows and its "
+                                      "decode kernel takes a bf16 query (--dtype=bf16, or the default cache)")
+        if sp_size_rank("sp")[0] > 1:
+            raise NotImplementedError("kv_dtype='fp8' with sp > 1: the 8-bit cache is not sharded over the sequence ring "
+                                      "(one rank, or the default cache)")
+        xq, xk, xv = xq.contiguous(), xk.contiguous(), xv.contiguous()
+        max_len = ck.shape[1]
+        if "index_dev" in cache:                   # hipGraph-capturable step: see _cached
+            if Q != 1:
+                raise NotImplementedError("kv_dtype='fp8' with Q > 1 at cache_index > 0: the 8-bit cache takes a prompt at "
+                                          "cache_index 0 and one token per step after it")
+            _ops.kv8_cache_write_at(ck, ks, xk, cache["index_dev"])
+            _ops.kv8_cache_write_at(cv, vs, xv, cache["index_dev"])
+            mask = (cache["mask_dev"][:, 0] != 0).to(torch.uint8).contiguous()
+        else:
+            idx = int(cache["cache_index"])
+            if idx == 0:
+                kvld = None if attention_mask is None else attention_mask[:, :Q]
+                out = ringattention_inference(xq, xk, xv, None, axis_name="sp", causal_offset=0, key_valid=kvld)
+                _ops.kv8_cache_write(ck, ks, xk, dst_row0=0)
+                _ops.kv8_cache_write(cv, vs, xv, dst_row0=0)
+                cache["cache_index"] = Q
+                return out
+            if Q != 1:
+                raise NotImplementedError("kv_dtype='fp8' with Q > 1 at cache_index > 0: the 8-bit cache takes a prompt at "
+                                          "cache_index 0 and one token per step after it")
+            _ops.kv8_cache_write(ck, ks, xk, dst_row0=idx)
+            _ops.kv8_cache_write(cv, vs, xv, dst_row0=idx)
+            cache["cache_index"] = idx + 1
+            mask = cached_visibility(B, 1, max_len, idx, attention_mask, xq.device)[:, 0].to(torch.uint8).contiguous()
+        o_parts, l_parts = _ops.attn_decode_kv8(xq, ck, ks, cv, vs, k_splits=_pick_splits(B, 1, H, max_len), dense_mask=mask)
+        return _ops.attn_combine(o_parts, l_parts, want_bf16=True)[0]
 
 
 class LLaMABlock(torch.nn.Module):
@@ -395,22 +440,44 @@ class LLaMAForCausalLM(torch.nn.Module):
             (x2,), ss = gemv_fused(swiglu(gate, up), (mlp.w2,), residual=x2, want_ss=True)
         return x2.reshape(B, 1, d)
 
-    def init_cache(self, batch_size, max_length, device=None):
+    def init_cache(self, batch_size, max_length, device=None, kv_dtype=None):
         """FlaxLLaMAPreTrainedModel.init_cache (lwm/llama.py:810-825): per layer, zeroed
-        (B, max_length, H, D) key/value caches and cache_index = 0."""
+        (B, max_length, H, D) key/value caches and cache_index = 0.
+        kv_dtype="fp8" (extension): the 8-bit cache of csrc/attn_decode_kv8.h -- per layer cached_key / cached_value as
+        uint8 e4m3fn bytes plus key_scale / value_scale (B, max_length, H) f32: 0.516 of the bytes, held and read per
+        decode step.  bf16 models on one rank; a prompt at cache_index 0, then one token per step."""
         device = device or self.wte.device
         H = self.cfg.num_attention_heads
         D = self.cfg.hidden_size // H
         n_sp = sp_size_rank("sp")[0]
         if max_length % n_sp:
             raise ValueError(f"max_length {max_length} is not divisible by the sp ring size {n_sp}")
+        if kv_dtype not in (None, "fp8"):
+            raise ValueError(f"kv_dtype={kv_dtype!r}: None (the model's dtype) or 'fp8'")
+        if kv_dtype == "fp8":
+            if self.dtype != torch.bfloat16:
+                raise NotImplementedError("kv_dtype='fp8' with a float32 model: the 8-bit cache quantises bf16 rows and its "
+                                          "decode kernel takes a bf16 query (--dtype=bf16, or the default cache)")
+            if n_sp > 1:
+                raise NotImplementedError("kv_dtype='fp8' with sp > 1: the 8-bit cache is not sharded over the sequence ring "
+                                          "(one rank, or the default cache)")
+            if D != 128:
+                raise NotImplementedError(f"kv_dtype='fp8': head_dim {D} (the 8-bit decode kernel is built for 128)")
+            q = lambda: torch.zeros(batch_size, max_length, H, D, dtype=torch.uint8, device=device)
+            sc = lambda: torch.ones(batch_size, max_length, H, dtype=torch.float32, device=device)
+            return [dict(cached_key=q(), cached_value=q(), key_scale=sc(), value_scale=sc(), cache_index=0) for _ in self.h]
         # sharded over "sp": each rank holds its contiguous max_length/sp rows (lwm/llama.py:454-467)
         z = lambda: torch.zeros(batch_size, max_length // n_sp, H, D, dtype=self.dtype, device=device)
         return [dict(cached_key=z(), cached_value=z(), cache_index=0) for _ in self.h]
 
+    @staticmethod
+    def device_index_cache(cache, index_dev):
+        """The per-layer cache dicts of a captured decode step: the same tensors, the row index on the device."""
+        return [{**{k: t for k, t in c.items() if k != "cache_index"}, "index_dev": index_dev} for c in cache]
+
     @torch.no_grad()
     def generate(self, input_ids, attention_mask=None, max_new_tokens=16, max_length=None, return_logits=False,
-                 graph=False):
+                 graph=False, kv_dtype=None):
         """Greedy decoding through the KV cache: prepare_inputs_for_generation /
         update_inputs_for_generation of the reference (lwm/llama.py:1113-1137) + argmax.
         Prefill writes the prompt's keys/values at cache_index 0 and attends over the whole
@@ -420,14 +487,18 @@ class LLaMAForCausalLM(torch.nn.Module):
         attention, MLP, and the head) is captured ONCE in a hipGraph and replayed per token; the
         cache index, position and current token advance on the device inside the graph.  A decode
         step is some 15 launches per layer of a few microseconds of work each -- launch-bound when
-        issued one by one.  Single-rank only (the cross-rank combine is not captured)."""
+        issued one by one.  Single-rank only (the cross-rank combine is not captured).
+
+        kv_dtype="fp8": the 8-bit KV cache (init_cache); the prompt attends over its own bf16 keys, every later
+        step over the quantised cache.  Works with graph=True."""
         B, S = input_ids.shape
         max_length = max_length or (S + max_new_tokens)
         dev = input_ids.device
         if graph and self.dtype == torch.float32:
             raise NotImplementedError("generate(graph=True) captures the bf16 decode kernels; a float32 model decodes eagerly "
                                       "(graph=False) through the f32 flavour of the attention op")
-        cache = self.init_cache(B, max_length, dev)
+        # (the default cache through the three-argument call every stand-in model answers)
+        cache = self.init_cache(B, max_length, dev) if kv_dtype is None else self.init_cache(B, max_length, dev, kv_dtype=kv_dtype)
         ext = torch.ones(B, max_length, dtype=torch.int32, device=dev)
         if attention_mask is not None:
             pos = attention_mask.to(torch.int32).cumsum(-1) - 1
@@ -460,7 +531,7 @@ class LLaMAForCausalLM(torch.nn.Module):
             idx = torch.tensor([int(cache[0]["cache_index"])], dtype=torch.int32, device=dev)
             ar = torch.arange(max_length, device=dev, dtype=torch.int32)
             tok, posd = step_in.clone(), pos.clone()
-            dcache = [dict(cached_key=c["cached_key"], cached_value=c["cached_value"], index_dev=idx) for c in cache]
+            dcache = self.device_index_cache(cache, idx)
 
             def step():
                 mask = ((ar[None, :] <= idx) & (ext > 0))[:, None, None, :]

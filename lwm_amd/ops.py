@@ -238,6 +238,97 @@ def kv_cache_write_at(cache, src, index_dev, *, row_offset=0, src_row0=0, nrows=
     return cache
 
 
+def _kv8_check(cache, scale, src):
+    """(e4m3 bytes (B,S,H,128) u8, scales (B,S,H) f32, bf16 source (B,*,H,128)) with contiguous rows"""
+    if not cache.is_cuda or cache.dtype != torch.uint8 or cache.dim() != 4 or not cache[0].is_contiguous():
+        raise ValueError("cache: expected a uint8 (B,S,H,D) device tensor of e4m3 bytes with contiguous (S,H,D)")
+    B, rows, H, D = cache.shape
+    if not scale.is_cuda or scale.dtype != torch.float32 or tuple(scale.shape) != (B, rows, H) or not scale[0].is_contiguous():
+        raise ValueError(f"scale: expected an f32 device tensor of shape {(B, rows, H)} with contiguous (S,H)")
+    if not src.is_cuda or src.dtype != torch.bfloat16 or src.dim() != 4 or not src[0].is_contiguous() or \
+            src.shape[0] != B or tuple(src.shape[2:]) != (H, D):
+        raise ValueError(f"src: expected a bf16 device tensor (B,*,H,D) = ({B},*,{H},{D}) with contiguous (S,H,D) "
+                         "(the 8-bit cache quantises bf16 rows; there is no float32 flavour)")
+    return B, rows, H, D
+
+
+def kv8_cache_write(cache, scale, src, *, dst_row0, src_row0=0, nrows=None):
+    """Quantise src[:, src_row0:src_row0+nrows] (bf16) into the 8-bit cache at row dst_row0: `cache` takes the e4m3fn
+    bytes, `scale` one power-of-two f32 per (row, head) (lwm_kv8_cache_write; the format: include/lwm_hip.h)."""
+    B, rows, H, D = _kv8_check(cache, scale, src)
+    if nrows is None:
+        nrows = src.shape[1] - src_row0
+    if dst_row0 < 0 or dst_row0 + nrows > rows or src_row0 < 0 or src_row0 + nrows > src.shape[1]:
+        raise ValueError("kv8_cache_write: row range out of bounds")
+    L = lib()
+    _capi.check(L, L.lwm_kv8_cache_write(cache.data_ptr(), src.data_ptr(), B, cache.stride(0), src.stride(0), dst_row0,
+                                         src_row0, nrows, H * D, scale.data_ptr(), scale.stride(0), H, _stream_ptr()),
+                "lwm_kv8_cache_write")
+    return cache, scale
+
+
+def kv8_cache_write_at(cache, scale, src, index_dev, *, row_offset=0, src_row0=0, nrows=None):
+    """The same with the destination row `index + row_offset` read from an int32 DEVICE tensor
+    (lwm_kv8_cache_write_at); rows that fall outside the cache are skipped."""
+    B, rows, H, D = _kv8_check(cache, scale, src)
+    if not index_dev.is_cuda or index_dev.dtype != torch.int32 or index_dev.numel() != 1:
+        raise ValueError("index_dev: expected a one-element int32 device tensor")
+    if nrows is None:
+        nrows = src.shape[1] - src_row0
+    if src_row0 < 0 or src_row0 + nrows > src.shape[1]:
+        raise ValueError("kv8_cache_write_at: source row range out of bounds")
+    L = lib()
+    _capi.check(L, L.lwm_kv8_cache_write_at(cache.data_ptr(), src.data_ptr(), B, cache.stride(0), src.stride(0),
+                                            index_dev.data_ptr(), row_offset, rows, src_row0, nrows, H * D,
+                                            scale.data_ptr(), scale.stride(0), H, _stream_ptr()),
+                "lwm_kv8_cache_write_at")
+    return cache, scale
+
+
+def kv8_dequant(q, scale):
+    """The numbers an 8-bit cache holds, as bf16: e4m3(q) * scale, exactly (4 significant bits times a power of two).
+    A torch expression for tests and debugging -- the decode kernel never materialises it."""
+    return (q.view(torch.float8_e4m3fn).float() * scale.unsqueeze(-1)).to(torch.bfloat16)
+
+
+def attn_decode_kv8(q, cached_key, key_scale, cached_value, value_scale, *, k_splits, dense_mask=None, scale=None):
+    """One query per batch row over the 8-bit cache (lwm_attn_decode_kv8): q bf16 (B,1,H,D); the cache as written by
+    kv8_cache_write; dense_mask u8 (B,1,Sk) or None.  Returns normalised partials (o_parts f32 [k_splits,B,1,H,D],
+    lse_parts f32 [k_splits,B,H,1]) -- merge with attn_combine."""
+    B, Sq, H, D = q.shape
+    if Sq != 1 or q.dtype != torch.bfloat16:
+        raise ValueError("attn_decode_kv8: expected a bf16 (B,1,H,D) query (the 8-bit cache serves one-token decode steps)")
+    a = _capi.LwmKv8DecodeArgs()
+    a.q = _t4(q, "q", torch.bfloat16)
+    Sk = cached_key.shape[1]
+    for n, c, s in (("key", cached_key, key_scale), ("value", cached_value, value_scale)):
+        if not c.is_cuda or c.dtype != torch.uint8 or tuple(c.shape) != (B, Sk, H, D) or c.stride(3) != 1:
+            raise ValueError(f"cached_{n}: expected a uint8 device tensor of shape {(B, Sk, H, D)} with contiguous D")
+        if not s.is_cuda or s.dtype != torch.float32 or tuple(s.shape) != (B, Sk, H) or s.stride(2) != 1:
+            raise ValueError(f"{n}_scale: expected an f32 device tensor of shape {(B, Sk, H)} with contiguous heads")
+    a.k, a.v = cached_key.data_ptr(), cached_value.data_ptr()
+    a.k_stride_b, a.k_stride_s, a.k_stride_h = cached_key.stride()[:3]
+    a.v_stride_b, a.v_stride_s, a.v_stride_h = cached_value.stride()[:3]
+    a.k_scale, a.v_scale = key_scale.data_ptr(), value_scale.data_ptr()
+    a.k_scale_stride_b, a.k_scale_stride_s = key_scale.stride()[:2]
+    a.v_scale_stride_b, a.v_scale_stride_s = value_scale.stride()[:2]
+    if dense_mask is not None:
+        m = dense_mask
+        if not m.is_cuda or m.dtype != torch.uint8 or tuple(m.shape) != (B, 1, Sk) or m.stride(2) != 1:
+            raise ValueError(f"dense_mask: expected a u8 device tensor of shape {(B, 1, Sk)} with contiguous keys")
+        a.dense_mask, a.mask_stride_b = m.data_ptr(), m.stride(0)
+    a.B, a.Sk, a.H, a.D = B, Sk, H, D
+    a.scale = float(scale) if scale is not None else 1.0 / math.sqrt(D)
+    k_splits = max(1, int(k_splits))
+    a.k_splits = k_splits
+    o_parts = torch.empty((k_splits, B, 1, H, D), dtype=torch.float32, device=q.device)
+    lse_parts = torch.empty((k_splits, B, H, 1), dtype=torch.float32, device=q.device)
+    a.out_acc, a.lse_acc = o_parts.data_ptr(), lse_parts.data_ptr()
+    L = lib()
+    _capi.check(L, L.lwm_attn_decode_kv8(C.byref(a), _stream_ptr()), "lwm_attn_decode_kv8")
+    return o_parts, lse_parts
+
+
 def bwd_stats_shape(B, H, Sq):
     """Shape of the backward's row statistics for a (B, Sq, H, D) query block: per (b, h) the rows
     [-lse * log2 e | -rowsum(dout * out)], padded to a multiple of 64 queries (lwm_attn_bwd_delta_bytes)."""
