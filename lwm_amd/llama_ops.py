@@ -42,14 +42,43 @@ def precompute_freqs_cis(dim: int, max_position_embedding: int, theta: float = 1
     return out.to(device) if device is not None else out
 
 
+def _on(t, ref):
+    """t lives on ref's ROCm device"""
+    return t.is_cuda and t.device == ref.device
+
+
+def _positions(position_ids, B, S, ref, who):
+    """position_ids -> contiguous int32 (B,S) on ref's device.  None = arange (lwm/llama.py:1081-1082).  A (1,S) or (B,1)
+    tensor is expanded: the reference gathers with jnp.take(freqs_cis, position_ids) (lwm/llama.py:515) and multiplies
+    the (.,S,1,D/2) result into (B,S,H,D/2), which broadcasts.  Anything else -- another rank, another length, a tensor on
+    another device, a non-integer dtype -- is refused: the kernel reads pos[b * S + s]."""
+    if not ref.is_cuda:
+        raise ValueError(f"{who}: expected ROCm device tensors (lwm_amd has no CPU path)")
+    if position_ids is None:
+        return torch.arange(S, device=ref.device, dtype=torch.int32)[None].expand(B, S).contiguous()
+    p = position_ids
+    if not torch.is_tensor(p) or p.is_floating_point() or p.is_complex() or p.dtype == torch.bool:
+        raise ValueError(f"{who}: position_ids must be an integer tensor")
+    if p.dim() != 2 or p.shape[0] not in (1, B) or p.shape[1] not in (1, S):
+        raise ValueError(f"{who}: position_ids must be broadcastable to {(B, S)} from (1 | B, 1 | S), got {tuple(p.shape)}")
+    if not _on(p, ref):
+        raise ValueError(f"{who}: position_ids must be on {ref.device}, got {p.device}")
+    return p.expand(B, S).to(torch.int32).contiguous()
+
+
+def _check_table(table, D, ref, who):
+    if not torch.is_tensor(table) or not _on(table, ref) or table.dtype != torch.float32 or not table.is_contiguous() or \
+            table.dim() != 3 or tuple(table.shape[1:]) != (D // 2, 2) or table.shape[0] < 1:
+        raise ValueError(f"{who}: freqs_cis must be the contiguous f32 (max_pos, {D // 2}, 2) table of precompute_freqs_cis "
+                         f"on {ref.device}")
+
+
 def _rope(x, table, pos, conj):
-    B, S, H, D = x.shape
-    if not x.is_cuda or x.dtype not in _DTYPES or x.stride(3) != 1:
+    if x.dim() != 4 or not x.is_cuda or x.dtype not in _DTYPES or x.stride(3) != 1:
         raise ValueError("rope: expected a bf16 / f32 (B,S,H,D) ROCm tensor with contiguous D")
-    if not table.is_cuda or table.dtype != torch.float32 or not table.is_contiguous() or \
-            tuple(table.shape[1:]) != (D // 2, 2):
-        raise ValueError(f"rope: table must be a contiguous f32 (max_pos, {D // 2}, 2) device tensor")
-    if pos.dtype != torch.int32 or not pos.is_contiguous() or tuple(pos.shape) != (B, S) or not pos.is_cuda:
+    B, S, H, D = x.shape
+    _check_table(table, D, x, "rope")
+    if pos.dtype != torch.int32 or not pos.is_contiguous() or tuple(pos.shape) != (B, S) or not _on(pos, x):
         raise ValueError(f"rope: position_ids must be contiguous int32 {(B, S)} on the device")
     y = torch.empty((B, S, H, D), dtype=x.dtype, device=x.device)
     L = lib()
@@ -72,23 +101,29 @@ class _Rope(torch.autograd.Function):
 
 def apply_rotary_emb(xq, xk, freqs_cis, position_ids=None, dtype=None):
     """lwm/llama.py:353-375 + the table gather of :515 (jnp.take(freqs_cis, position_ids)).
-    xq, xk: (B,S,H,D) bf16; freqs_cis from precompute_freqs_cis; position_ids (B,S) int
+    xq, xk: (B,S,H,D) bf16; freqs_cis from precompute_freqs_cis; position_ids (B,S) or (1,S) int on the device
     (default arange, as lwm/llama.py:1081-1082)."""
+    if xq.dim() != 4 or xk.dim() != 4 or xq.shape[:2] != xk.shape[:2] or xq.shape[3] != xk.shape[3]:
+        raise ValueError("apply_rotary_emb: xq and xk must be (B,S,H,D) with the same B, S and D")
+    if not xq.is_cuda or xk.device != xq.device or xq.dtype not in _DTYPES or xk.dtype != xq.dtype or xq.stride(3) != 1 or \
+            xk.stride(3) != 1:
+        raise ValueError("apply_rotary_emb: xq and xk must be bf16 / f32 tensors of one dtype on one ROCm device, D contiguous")
     B, S = xq.shape[:2]
-    if position_ids is None:
-        position_ids = torch.arange(S, device=xq.device, dtype=torch.int32)[None].expand(B, S)
-    pos = position_ids.to(torch.int32).contiguous()
+    pos = _positions(position_ids, B, S, xq, "apply_rotary_emb")
     return _Rope.apply(xq, freqs_cis, pos), _Rope.apply(xk, freqs_cis, pos)
 
 
 class _RmsNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, eps):
-        if not x.is_cuda or x.dtype not in _DTYPES or not x.is_contiguous():
+        if not x.is_cuda or x.dtype not in _DTYPES or not x.is_contiguous() or x.dim() < 1:
             raise ValueError("RMSNorm: expected a contiguous bf16 / f32 ROCm tensor")
         Cc = x.shape[-1]
-        rows = x.numel() // Cc
-        w = weight.to(x.dtype).contiguous()
+        rows = x.numel() // Cc if Cc else 0
+        if not _on(weight, x) or not weight.is_floating_point() or weight.numel() != Cc:
+            raise ValueError(f"RMSNorm: weight must be a floating-point tensor of {Cc} elements on {x.device}, got "
+                             f"{tuple(weight.shape)} {weight.dtype} on {weight.device}")
+        w = weight.reshape(Cc).to(x.dtype).contiguous()
         y = torch.empty_like(x)
         rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
         L = lib()
@@ -129,9 +164,14 @@ class RMSNorm(torch.nn.Module):
 
 # ---------------------------------------------------------------- loss (lwm/train.py:177-202)
 def _softmax_ce(logits2d, target, weight, want_grad):
+    if logits2d.dim() != 2 or not logits2d.is_cuda or logits2d.dtype not in _DTYPES or not logits2d.is_contiguous():
+        raise ValueError("cross entropy: expected contiguous bf16 / f32 (rows, V) ROCm logits")
     rows, V = logits2d.shape
-    if not logits2d.is_cuda or logits2d.dtype not in _DTYPES or not logits2d.is_contiguous():
-        raise ValueError("cross entropy: expected contiguous bf16 / f32 ROCm logits")
+    if not _on(target, logits2d) or target.dtype != torch.int32 or not target.is_contiguous() or target.numel() != rows:
+        raise ValueError(f"cross entropy: target must be a contiguous int32 tensor of {rows} elements on {logits2d.device}")
+    if weight is not None and (not _on(weight, logits2d) or weight.dtype != torch.float32 or not weight.is_contiguous() or
+                               weight.numel() != rows):
+        raise ValueError(f"cross entropy: weight must be a contiguous f32 tensor of {rows} elements on {logits2d.device}")
     nll = torch.empty(rows, dtype=torch.float32, device=logits2d.device)
     correct = torch.empty(rows, dtype=torch.int32, device=logits2d.device)
     dl = torch.empty_like(logits2d) if want_grad else None
@@ -143,6 +183,13 @@ def _softmax_ce(logits2d, target, weight, want_grad):
     return nll, correct, dl
 
 
+def _check_tokens(tokens, B, S, ref, who):
+    """tokens: an integer (B,S) tensor on ref's device (the kernel reads target[b * S + s])"""
+    if not torch.is_tensor(tokens) or tokens.is_floating_point() or tokens.dtype == torch.bool or \
+            tuple(tokens.shape) != (B, S) or tokens.device != ref.device:
+        raise ValueError(f"{who}: tokens must be an integer tensor of shape {(B, S)} on {ref.device}")
+
+
 def _row_weights(valid, B, S, device, sp_sharded=True):
     """valid (B,S) or None -> (valid f32, per-row gradient weight valid / (max(sum_s valid, 1e-10) * B)).
     Over a sequence ring S is this rank's SHARD of each sequence: the count of valid targets is summed over the "sp"
@@ -152,6 +199,8 @@ def _row_weights(valid, B, S, device, sp_sharded=True):
     collective), and the rows are this rank's shard.  A loss on tokens that are REPLICATED on the sp ranks (evaluation,
     scoring) must say sp_sharded=False: no collective, the count is the local one -- with the default the count would
     come out n times too large and the loss n times too small, without any error."""
+    if valid is not None and (tuple(valid.shape) != (B, S) or valid.device != torch.device(device)):
+        raise ValueError(f"cross entropy: valid must have shape {(B, S)} on {device}, got {tuple(valid.shape)} on {valid.device}")
     v = torch.ones(B, S, dtype=torch.float32, device=device) if valid is None else valid.to(torch.float32)
     count = v.sum(dim=-1, keepdim=True)
     if sp_sharded:
@@ -164,7 +213,10 @@ def _row_weights(valid, B, S, device, sp_sharded=True):
 class _CrossEntropy(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, tokens, valid, sp_sharded=True):
+        if logits.dim() != 3 or not logits.is_cuda or logits.dtype not in _DTYPES:
+            raise ValueError("cross entropy: expected bf16 / f32 (B,S,V) ROCm logits")
         B, S, V = logits.shape
+        _check_tokens(tokens, B, S, logits, "cross entropy")
         v, w = _row_weights(valid, B, S, logits.device, sp_sharded)
         nll, correct, dl = _softmax_ce(logits.reshape(B * S, V), tokens.reshape(-1).to(torch.int32).contiguous(),
                                        w.reshape(-1), logits.requires_grad)
@@ -197,8 +249,16 @@ class _ChunkedHeadLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, hidden, kernel, tokens, valid, chunk, sp_sharded=True):
+        if hidden.dim() != 3 or not hidden.is_cuda or hidden.dtype not in _DTYPES:
+            raise ValueError("chunked_lm_head_loss: expected bf16 / f32 (B,S,d_model) ROCm hidden states")
         B, S, Dm = hidden.shape
+        if kernel.dim() != 2 or kernel.shape[0] != Dm or not _on(kernel, hidden) or not kernel.is_floating_point():
+            raise ValueError(f"chunked_lm_head_loss: lm_head_kernel must be a floating-point ({Dm}, vocab) tensor on "
+                             f"{hidden.device}")
+        if chunk < 1:
+            raise ValueError("chunked_lm_head_loss: chunk must be >= 1")
         V = kernel.shape[1]
+        _check_tokens(tokens, B, S, hidden, "chunked_lm_head_loss")
         v, w = _row_weights(valid, B, S, hidden.device, sp_sharded)
         tok = tokens.to(torch.int32)
         need = hidden.requires_grad or kernel.requires_grad
@@ -256,6 +316,8 @@ class _SwiGLU(torch.autograd.Function):
         for t in (a, b):
             if not t.is_cuda or t.dtype not in _DTYPES or t.dtype != a.dtype or not t.is_contiguous():
                 raise ValueError("swiglu: expected contiguous bf16 / f32 ROCm tensors of one dtype")
+        if b.shape != a.shape or b.device != a.device:
+            raise ValueError(f"swiglu: b must have a's shape {tuple(a.shape)} on {a.device}, got {tuple(b.shape)} on {b.device}")
         y = torch.empty_like(a)
         L = lib()
         _capi.check(L, _fn(L, "swiglu_fwd", a.dtype)(a.data_ptr(), b.data_ptr(), y.data_ptr(), a.numel(), _stream_ptr()),
@@ -282,14 +344,27 @@ def swiglu(a, b):
 _GEMV_WS = {}
 
 
+def _gemv_check(x, kernels, out_dtype):
+    """x (rows, K) bf16 with contiguous rows, 1..3 contiguous bf16 (K, N_i) kernels, all on x's ROCm device -> (rows, K)"""
+    if x.dim() != 2 or not x.is_cuda or x.dtype != torch.bfloat16 or x.stride(1) != 1:
+        raise ValueError("gemv: x must be a bf16 (rows, K) ROCm tensor with contiguous rows")
+    rows, K = x.shape
+    if not 1 <= len(kernels) <= 3:
+        raise ValueError("gemv: one to three kernels per call")
+    for i, k in enumerate(kernels):
+        if k.dim() != 2 or not _on(k, x) or k.dtype != torch.bfloat16 or not k.is_contiguous() or k.shape[0] != K:
+            raise ValueError(f"gemv: kernels[{i}] must be a contiguous bf16 ({K}, N) tensor on {x.device}, got "
+                             f"{tuple(k.shape)} {k.dtype} on {k.device}")
+    if out_dtype not in _DTYPES:
+        raise ValueError("gemv: out_dtype must be torch.bfloat16 or torch.float32")
+    return rows, K
+
+
 def gemv_multi(x, kernels, out_dtype=torch.bfloat16):
     """x (rows <= 4, K) bf16 against 1..3 kernels (K, N_i) bf16 that share it -> [(rows, N_i)] in `out_dtype`
     (bf16 or f32) through ONE lwm_gemv_multi_bf16 call: every kernel streamed once from HBM, f32 accumulation
     along a fixed tree."""
-    rows, K = x.shape
-    if x.dtype != torch.bfloat16 or x.stride(1) != 1 or any(
-            k.dtype != torch.bfloat16 or not k.is_contiguous() or k.shape[0] != K for k in kernels):
-        raise ValueError("gemv: expected bf16 x (contiguous rows) and contiguous bf16 (K, N) kernels")
+    rows, K = _gemv_check(x, kernels, out_dtype)
     L = lib()
     n = len(kernels)
     Ns = [int(k.shape[1]) for k in kernels]
@@ -318,10 +393,7 @@ def gemv_fused(x, kernels, *, norm=None, residual=None, want_ss=False, out_dtype
     norm = (ss (rows, n <= 64) f32 partial sums of squares of x's rows, weight (K,) bf16, eps): RMSNorm on load;
     residual (rows, N) bf16 (one kernel): y = bf16(bf16(x @ W) + residual); want_ss: also return the (rows, N / 128)
     partial sums of squares of y for the next norm.  -> [y_i] or ([y_i], ss)."""
-    rows, K = x.shape
-    if x.dtype != torch.bfloat16 or x.stride(1) != 1 or any(
-            k.dtype != torch.bfloat16 or not k.is_contiguous() or k.shape[0] != K for k in kernels):
-        raise ValueError("gemv: expected bf16 x (contiguous rows) and contiguous bf16 (K, N) kernels")
+    rows, K = _gemv_check(x, kernels, out_dtype)
     L = lib()
     n = len(kernels)
     Ns = [int(k.shape[1]) for k in kernels]
@@ -342,13 +414,16 @@ def gemv_fused(x, kernels, *, norm=None, residual=None, want_ss=False, out_dtype
             a.y[i], a.ldy[i] = ys[i].data_ptr(), Ns[i]
     if norm is not None:
         ss, w, eps = norm
-        if ss.dtype != torch.float32 or not ss.is_contiguous() or ss.shape[0] != rows or ss.shape[1] > 64 or \
-                w.dtype != torch.bfloat16 or not w.is_contiguous() or w.numel() != K:
-            raise ValueError("gemv_fused: norm = (ss (rows, n <= 64) f32 contiguous, weight (K,) bf16, eps)")
+        if not _on(ss, x) or ss.dtype != torch.float32 or not ss.is_contiguous() or ss.dim() != 2 or ss.shape[0] != rows or \
+                not 1 <= ss.shape[1] <= 64:
+            raise ValueError(f"gemv_fused: norm ss must be a contiguous f32 ({rows}, n <= 64) tensor on {x.device}")
+        if not _on(w, x) or w.dtype != torch.bfloat16 or not w.is_contiguous() or w.numel() != K:
+            raise ValueError(f"gemv_fused: norm weight must be a contiguous bf16 tensor of {K} elements on {x.device}")
         a.norm_weight, a.ss_in, a.ss_n, a.eps = w.data_ptr(), ss.data_ptr(), ss.shape[1], float(eps)
     if residual is not None:
-        if n != 1 or residual.dtype != torch.bfloat16 or tuple(residual.shape) != (rows, Ns[0]) or residual.stride(1) != 1:
-            raise ValueError("gemv_fused: residual goes with ONE kernel and has its output's shape")
+        if n != 1 or not _on(residual, x) or residual.dtype != torch.bfloat16 or tuple(residual.shape) != (rows, Ns[0]) or \
+                residual.stride(1) != 1:
+            raise ValueError(f"gemv_fused: residual goes with ONE kernel and is a bf16 tensor of its output's shape on {x.device}")
         a.residual[0], a.ldres[0] = residual.data_ptr(), residual.stride(0)
     ss_out = None
     if want_ss:
@@ -455,6 +530,8 @@ def transpose2d(src, out=None):
     R, Cc = src.shape
     if out is None:
         out = torch.empty(Cc, R, dtype=src.dtype, device=src.device)
+    elif tuple(out.shape) != (Cc, R) or out.dtype != src.dtype or out.device != src.device:
+        raise ValueError(f"transpose2d: out must be a {(Cc, R)} {src.dtype} tensor on {src.device}")
     if (src.is_cuda and src.dtype == torch.bfloat16 and src.stride(1) == 1 and out.stride(1) == 1 and R % 64 == 0 and
             Cc % 64 == 0 and src.stride(0) % 8 == 0 and out.stride(0) % 8 == 0 and src.data_ptr() % 16 == 0 and
             out.data_ptr() % 16 == 0):
@@ -475,6 +552,9 @@ def wgrad(x2, g2):
     operands read where they lie, csrc/gemm_wgrad.h; 1.1-1.2 PF/s against the library's 0.9-1.05 in this layout and
     1.1-1.17 behind a transposed copy of the narrow operand -- profiles/r06_wgrad.md); anything else -> the narrow operand
     transposed by lwm_transpose_bf16 and a library GEMM.  LWM_WGRAD_HIP=0: the library form throughout."""
+    if x2.dim() != 2 or g2.dim() != 2 or g2.shape[0] != x2.shape[0] or g2.dtype != x2.dtype or g2.device != x2.device:
+        raise ValueError(f"wgrad: x2 (M, K) and g2 (M, N) must share M, dtype and device, got {tuple(x2.shape)} {x2.dtype} "
+                         f"on {x2.device} and {tuple(g2.shape)} {g2.dtype} on {g2.device}")
     M, K = x2.shape
     N = g2.shape[1]
     if x2.dtype == torch.float32:
@@ -622,13 +702,18 @@ class _QKVRope(torch.autograd.Function):
 
 def qkv_rope(x, wq, wk, wv, freqs_cis, position_ids, num_heads):
     """FlaxLLaMAAttention's projections + head split + apply_rotary_emb (lwm/llama.py:494-520) as one operator."""
-    B, S = x.shape[:2]
-    if position_ids is None:
-        position_ids = torch.arange(S, device=x.device, dtype=torch.int32)[None].expand(B, S)
-    pos = position_ids.to(torch.int32).contiguous()
-    if not freqs_cis.is_cuda or freqs_cis.dtype != torch.float32 or not freqs_cis.is_contiguous():
-        raise ValueError("qkv_rope: freqs_cis must be the contiguous f32 device table of precompute_freqs_cis")
-    return _QKVRope.apply(x, wq, wk, wv, freqs_cis, pos, int(num_heads))
+    H = int(num_heads)
+    if x.dim() != 3 or not x.is_cuda or x.dtype != torch.bfloat16:
+        raise ValueError("qkv_rope: x must be a bf16 (B,S,d_model) ROCm tensor (the fused projection is the bf16 path)")
+    B, S, d = x.shape
+    for n, w in (("wq", wq), ("wk", wk), ("wv", wv)):
+        if w.dim() != 2 or not _on(w, x) or w.dtype != torch.bfloat16 or tuple(w.shape) != (d, wq.shape[1]):
+            raise ValueError(f"qkv_rope: {n} must be a bf16 ({d}, H * D) tensor on {x.device}, the three of one shape")
+    if H < 1 or wq.shape[1] % H or (wq.shape[1] // H) % 8:
+        raise ValueError(f"qkv_rope: {wq.shape[1]} output features do not split into {H} heads of a multiple of 8")
+    _check_table(freqs_cis, wq.shape[1] // H, x, "qkv_rope")
+    pos = _positions(position_ids, B, S, x, "qkv_rope")
+    return _QKVRope.apply(x, wq, wk, wv, freqs_cis, pos, H)
 
 
 class _RmsNormRes(torch.autograd.Function):
@@ -638,6 +723,8 @@ class _RmsNormRes(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, eps):
+        if x.dtype != torch.bfloat16:
+            raise ValueError("rmsnorm_residual: expected a bf16 ROCm tensor (its backward kernel is the bf16 one)")
         y = _RmsNorm.forward(ctx, x, weight, eps)
         ctx.set_materialize_grads(False)
         return y, x.view_as(x)
@@ -672,6 +759,8 @@ class _SwiGLUHalves(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y13):
+        if y13.dim() < 1 or y13.shape[-1] % 2:
+            raise ValueError("swiglu_halves: expected a bf16 ROCm tensor (..., 2F) with F % 8 == 0")
         F2 = y13.shape[-1]
         F = F2 // 2
         y2 = y13.reshape(-1, F2)

@@ -27,12 +27,17 @@ def _stream_ptr(stream=None):
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def _t4(t, name, dtype=None):
-    """(B,S,H,D) bf16 -- or f32, the fp32 flavour of the op -- device tensor -> LwmTensor4; `dtype`: the one it must have"""
+def _t4(t, name, dtype=None, shape=None, like=None):
+    """(B,S,H,D) bf16 -- or f32, the fp32 flavour of the op -- device tensor -> LwmTensor4; `dtype`: the one it must have;
+    `shape`: the one it must have; `like`: a tensor whose device it must share"""
     if t is None:
         return _capi.LwmTensor4(None, 0, 0, 0)
     if not t.is_cuda:
         raise ValueError(f"{name}: expected a ROCm device tensor (lwm_amd has no CPU path)")
+    if like is not None and t.device != like.device:
+        raise ValueError(f"{name}: expected a tensor on {like.device}, got {t.device}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
     if t.dtype not in ((torch.bfloat16, torch.float32) if dtype is None else (dtype,)) or t.dim() != 4 or t.stride(3) != 1:
         raise ValueError(f"{name}: expected {'bf16 / f32' if dtype is None else dtype} (B,S,H,D) with contiguous D, got "
                          f"{t.dtype} {tuple(t.shape)} strides {t.stride()}")
@@ -45,11 +50,11 @@ def _entry(L, name, dtype):
     return getattr(L, name + "_f32") if dtype == torch.float32 else getattr(L, name)
 
 
-def _f32(t, name, shape=None):
+def _f32(t, name, shape=None, like=None):
     if t is None:
         return None
-    if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
-        raise ValueError(f"{name}: expected a contiguous f32 device tensor")
+    if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or (like is not None and t.device != like.device):
+        raise ValueError(f"{name}: expected a contiguous f32 device tensor" + ("" if like is None else f" on {like.device}"))
     if shape is not None and tuple(t.shape) != tuple(shape):
         raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
     return t.data_ptr()
@@ -59,10 +64,13 @@ def _base(q, k, v, *, q_start, k_start, causal, seg_q, seg_k, key_valid, scale, 
     """q_piece2 / k_piece2 = (cut row, position of that row) -- or a list of such cuts, in ascending order: the pieces of
     LwmAttnArgs' piecewise position maps beyond the first (rows before the first cut sit at *_start + row, rows from a cut
     on at its position + (row - cut); cuts are multiples of 256 rows)"""
-    B, Sq, H, D = q.shape
-    Sk = k.shape[1]
     a = _capi.LwmAttnArgs()
-    a.q, a.k, a.v = _t4(q, "q"), _t4(k, "k", q.dtype), _t4(v, "v", q.dtype)
+    a.q = _t4(q, "q")
+    B, Sq, H, D = q.shape
+    if k.dim() != 4:
+        raise ValueError(f"k: expected (B,Sk,H,D), got {tuple(k.shape)}")
+    Sk = k.shape[1]
+    a.k, a.v = _t4(k, "k", q.dtype, (B, Sk, H, D), q), _t4(v, "v", q.dtype, (B, Sk, H, D), q)
     a.B, a.H, a.Sq, a.Sk, a.D = B, H, Sq, Sk, D
     a.q_start, a.k_start = int(q_start), int(k_start)
     cuts = lambda c: [c] if isinstance(c, tuple) else list(c)
@@ -76,20 +84,28 @@ def _base(q, k, v, *, q_start, k_start, causal, seg_q, seg_k, key_valid, scale, 
         raise ValueError("seg_q and seg_k must be given together")
     if seg_q is not None:
         for n, s, L in (("seg_q", seg_q, Sq), ("seg_k", seg_k, Sk)):
-            if s.dtype != torch.int32 or not s.is_contiguous() or tuple(s.shape) != (B, L) or not s.is_cuda:
-                raise ValueError(f"{n}: expected contiguous int32 device tensor of shape {(B, L)}")
+            if s.dtype != torch.int32 or not s.is_contiguous() or tuple(s.shape) != (B, L) or s.device != q.device:
+                raise ValueError(f"{n}: expected contiguous int32 tensor of shape {(B, L)} on {q.device}")
         a.segment_ids_q, a.segment_ids_k = seg_q.data_ptr(), seg_k.data_ptr()
     if key_valid is not None:
         if key_valid.dtype != torch.uint8 or not key_valid.is_contiguous() or \
-                tuple(key_valid.shape) != (B, Sk) or not key_valid.is_cuda:
-            raise ValueError(f"key_valid: expected contiguous uint8 device tensor of shape {(B, Sk)}")
+                tuple(key_valid.shape) != (B, Sk) or key_valid.device != q.device:
+            raise ValueError(f"key_valid: expected contiguous uint8 tensor of shape {(B, Sk)} on {q.device}")
         a.key_valid = key_valid.data_ptr()
     if seg_q is not None and SEGMENT_SKIP and q.dtype == torch.bfloat16:
-        # block-sparsity hints: whole documents of a packed batch are skipped in-kernel (the f32 kernels do not read them)
+        a._hint_src = (seg_q, seg_k, key_valid)
+    return a
+
+
+def _set_hints(a):
+    """block-sparsity hints: whole documents of a packed batch are skipped in-kernel (the f32 kernels do not read them).
+    Computed by a launch of their own, hence LAST: after every operand of the call has passed its checks."""
+    src = getattr(a, "_hint_src", None)
+    if src is not None:
+        seg_q, seg_k, key_valid = src
         bq, bk = _cached_segment_blocks(seg_q, None), _cached_segment_blocks(seg_k, key_valid)
         a.seg_blocks_q, a.seg_blocks_k = bq.data_ptr(), bk.data_ptr()
         a._keep = (bq, bk)
-    return a
 
 
 def _cached_segment_blocks(seg, valid):
@@ -110,6 +126,11 @@ SEGMENT_SKIP = True   # set False to A/B the in-kernel document skipping
 
 def segment_blocks(seg, valid=None):
     """(min, max) segment id per block of 32 rows -> int32 (B, ceil(S/32), 2) (lwm_attn_segment_blocks)."""
+    if not seg.is_cuda or seg.dtype != torch.int32 or seg.dim() != 2 or not seg.is_contiguous():
+        raise ValueError("segment_blocks: seg must be a contiguous int32 (B,S) device tensor")
+    if valid is not None and (valid.device != seg.device or valid.dtype != torch.uint8 or valid.shape != seg.shape or
+                              not valid.is_contiguous()):
+        raise ValueError(f"segment_blocks: valid must be a contiguous uint8 tensor of shape {tuple(seg.shape)} on {seg.device}")
     B, S = seg.shape
     out = torch.empty((B, (S + 31) // 32, 2), dtype=torch.int32, device=seg.device)
     L = lib()
@@ -127,33 +148,35 @@ def attn_fwd_block(q, k, v, *, q_start=0, k_start=0, causal=True, seg_q=None, se
     B, Sq, H, D = q.shape
     a = _base(q, k, v, q_start=q_start, k_start=k_start, causal=causal, seg_q=seg_q, seg_k=seg_k,
               key_valid=key_valid, scale=scale, q_piece2=q_piece2, k_piece2=k_piece2)
-    _set_dense_mask(a, dense_mask, B, Sq, k.shape[1])
+    _set_dense_mask(a, dense_mask, B, Sq, k.shape[1], q)
     if final:
         if out is None:
             out = torch.empty((B, Sq, H, D), dtype=q.dtype, device=q.device)
         if lse is None:
             lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
-        a.out = _t4(out, "out", q.dtype)
-        a.lse = _f32(lse, "lse", (B, H, Sq))
+        a.out = _t4(out, "out", q.dtype, (B, Sq, H, D), q)
+        a.lse = _f32(lse, "lse", (B, H, Sq), q)
     else:
         if out_acc is None:
             out_acc = torch.empty((B, Sq, H, D), dtype=torch.float32, device=q.device)
         if lse_acc is None:
             lse_acc = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
-    a.out_acc = _f32(out_acc, "out_acc", (B, Sq, H, D))
-    a.lse_acc = _f32(lse_acc, "lse_acc", (B, H, Sq))
+    a.out_acc = _f32(out_acc, "out_acc", (B, Sq, H, D), q)
+    a.lse_acc = _f32(lse_acc, "lse_acc", (B, H, Sq), q)
     a.carry_in = int(bool(carry_in))
     a.final_out = int(bool(final))
+    _set_hints(a)
     L = lib()
     _capi.check(L, _entry(L, "lwm_attn_fwd", q.dtype)(C.byref(a), _stream_ptr()), "lwm_attn_fwd")
     return (out, lse) if final else (out_acc, lse_acc)
 
 
-def _set_dense_mask(a, dense_mask, B, Sq, Sk):
+def _set_dense_mask(a, dense_mask, B, Sq, Sk, like=None):
     if dense_mask is None:
         return
     m = dense_mask
-    if not m.is_cuda or m.dtype != torch.uint8 or tuple(m.shape) != (B, Sq, Sk) or m.stride(2) != 1:
+    if not m.is_cuda or m.dtype != torch.uint8 or tuple(m.shape) != (B, Sq, Sk) or m.stride(2) != 1 or \
+            (like is not None and m.device != like.device):
         raise ValueError(f"dense_mask: expected a u8 device tensor of shape {(B, Sq, Sk)} with contiguous keys")
     a.dense_mask, a.mask_stride_b, a.mask_stride_q = m.data_ptr(), m.stride(0), m.stride(1)
 
@@ -168,12 +191,13 @@ def attn_fwd_splitk(q, k, v, *, k_splits, q_start=0, k_start=0, causal=False, se
         raise ValueError("attn_fwd_splitk: the inference kernels take bf16 operands (the f32 flavour serves the training op)")
     a = _base(q, k, v, q_start=q_start, k_start=k_start, causal=causal, seg_q=seg_q, seg_k=seg_k,
               key_valid=key_valid, scale=scale)
-    _set_dense_mask(a, dense_mask, B, Sq, k.shape[1])
+    _set_dense_mask(a, dense_mask, B, Sq, k.shape[1], q)
     k_splits = max(1, int(k_splits))
     o_parts = torch.empty((k_splits, B, Sq, H, D), dtype=torch.float32, device=q.device)
     lse_parts = torch.empty((k_splits, B, H, Sq), dtype=torch.float32, device=q.device)
     a.out_acc, a.lse_acc = o_parts.data_ptr(), lse_parts.data_ptr()
     a.carry_in, a.final_out, a.k_splits = 0, 0, k_splits
+    _set_hints(a)
     L = lib()
     _capi.check(L, L.lwm_attn_fwd(C.byref(a), _stream_ptr()), "lwm_attn_fwd")
     return o_parts, lse_parts
@@ -181,6 +205,8 @@ def attn_fwd_splitk(q, k, v, *, k_splits, q_start=0, k_start=0, causal=False, se
 
 def attn_combine(o_parts, lse_parts, *, out=None, out_f32=None, lse=None, want_bf16=True):
     """Merge normalised partials (lwm_attn_combine).  Returns (out bf16 or f32, lse)."""
+    if not torch.is_tensor(o_parts) or o_parts.dim() != 5:
+        raise ValueError("o_parts: expected a contiguous f32 (P,B,Sq,H,D) device tensor")
     P, B, Sq, H, D = o_parts.shape
     if lse is None:
         lse = torch.empty((B, H, Sq), dtype=torch.float32, device=o_parts.device)
@@ -188,11 +214,12 @@ def attn_combine(o_parts, lse_parts, *, out=None, out_f32=None, lse=None, want_b
         out = torch.empty((B, Sq, H, D), dtype=torch.bfloat16, device=o_parts.device)
     if not want_bf16 and out_f32 is None:
         out_f32 = torch.empty((B, Sq, H, D), dtype=torch.float32, device=o_parts.device)
+    args = (_f32(o_parts, "o_parts"), _f32(lse_parts, "lse_parts", (P, B, H, Sq), o_parts), P,
+            _t4(out, "out", torch.bfloat16, (B, Sq, H, D), o_parts) if want_bf16 else _capi.LwmTensor4(None, 0, 0, 0),
+            None if want_bf16 else _f32(out_f32, "out_f32", (B, Sq, H, D), o_parts),
+            _f32(lse, "lse", (B, H, Sq), o_parts), B, Sq, H, D)
     L = lib()
-    _capi.check(L, L.lwm_attn_combine(_f32(o_parts, "o_parts"), _f32(lse_parts, "lse_parts", (P, B, H, Sq)), P,
-                                      _t4(out, "out", torch.bfloat16) if want_bf16 else _capi.LwmTensor4(None, 0, 0, 0),
-                                      None if want_bf16 else _f32(out_f32, "out_f32"),
-                                      _f32(lse, "lse", (B, H, Sq)), B, Sq, H, D, _stream_ptr()),
+    _capi.check(L, L.lwm_attn_combine(*args, _stream_ptr()),
                 "lwm_attn_combine")
     return (out if want_bf16 else out_f32), lse
 
@@ -206,9 +233,12 @@ def kv_cache_write(cache, src, *, dst_row0, src_row0=0, nrows=None):
                 not t[0].is_contiguous():
             raise ValueError(f"{n}: expected bf16 / f32 (B,S,H,D) device tensors of one dtype with contiguous (S,H,D)")
     B, _, H, D = cache.shape
+    if src.device != cache.device or src.shape[0] != B or tuple(src.shape[2:]) != (H, D):
+        raise ValueError(f"src: expected a (B,*,H,D) = ({B},*,{H},{D}) tensor on {cache.device}, got {tuple(src.shape)} on "
+                         f"{src.device}")
     if nrows is None:
         nrows = src.shape[1] - src_row0
-    if dst_row0 < 0 or dst_row0 + nrows > cache.shape[1] or src_row0 + nrows > src.shape[1]:
+    if nrows < 0 or dst_row0 < 0 or dst_row0 + nrows > cache.shape[1] or src_row0 < 0 or src_row0 + nrows > src.shape[1]:
         raise ValueError("kv_cache_write: row range out of bounds")
     w = cache.element_size() // 2            # bf16-sized units per element
     L = lib()
@@ -224,12 +254,15 @@ def kv_cache_write_at(cache, src, index_dev, *, row_offset=0, src_row0=0, nrows=
     for n, t in (("cache", cache), ("src", src)):
         if not t.is_cuda or t.dtype != torch.bfloat16 or t.dim() != 4 or not t[0].is_contiguous():
             raise ValueError(f"{n}: expected bf16 (B,S,H,D) device tensor with contiguous (S,H,D)")
-    if not index_dev.is_cuda or index_dev.dtype != torch.int32 or index_dev.numel() != 1:
+    if index_dev.device != cache.device or index_dev.dtype != torch.int32 or index_dev.numel() != 1:
         raise ValueError("index_dev: expected a one-element int32 device tensor")
     B, rows, H, D = cache.shape
+    if src.device != cache.device or src.shape[0] != B or tuple(src.shape[2:]) != (H, D):
+        raise ValueError(f"src: expected a (B,*,H,D) = ({B},*,{H},{D}) tensor on {cache.device}, got {tuple(src.shape)} on "
+                         f"{src.device}")
     if nrows is None:
         nrows = src.shape[1] - src_row0
-    if src_row0 < 0 or src_row0 + nrows > src.shape[1]:
+    if nrows < 0 or src_row0 < 0 or src_row0 + nrows > src.shape[1]:
         raise ValueError("kv_cache_write_at: source row range out of bounds")
     L = lib()
     _capi.check(L, L.lwm_kv_cache_write_at(cache.data_ptr(), src.data_ptr(), B, cache.stride(0), src.stride(0),
@@ -337,14 +370,15 @@ def bwd_stats_shape(B, H, Sq):
 
 def attn_bwd_delta(out, dout, lse, delta=None):
     """The row statistics the backward kernels consume (lwm_attn_bwd_delta), from out, dout and the forward's lse."""
+    a = _capi.LwmAttnArgs()
+    a.out = _t4(out, "out")
     B, Sq, H, D = out.shape
     if delta is None:
         delta = torch.empty(bwd_stats_shape(B, H, Sq), dtype=torch.float32, device=out.device)
-    a = _capi.LwmAttnArgs()
-    a.out, a.dout = _t4(out, "out"), _t4(dout, "dout", out.dtype)
+    a.dout = _t4(dout, "dout", out.dtype, (B, Sq, H, D), out)
     a.B, a.H, a.Sq, a.Sk, a.D = B, H, Sq, 0, D
-    a.lse = _f32(lse, "lse", (B, H, Sq))
-    a.delta = _f32(delta, "delta", bwd_stats_shape(B, H, Sq))
+    a.lse = _f32(lse, "lse", (B, H, Sq), out)
+    a.delta = _f32(delta, "delta", bwd_stats_shape(B, H, Sq), out)
     a.delta_bytes = delta.numel() * 4
     L = lib()
     _capi.check(L, _entry(L, "lwm_attn_bwd_delta", out.dtype)(C.byref(a), _stream_ptr()), "lwm_attn_bwd_delta")
@@ -352,11 +386,11 @@ def attn_bwd_delta(out, dout, lse, delta=None):
 
 
 def _bwd_base(q, k, v, dout, lse, delta, kw):
-    B, Sq, H, D = q.shape
     a = _base(q, k, v, **kw)
-    a.dout = _t4(dout, "dout", q.dtype)
-    a.lse = _f32(lse, "lse", (B, H, Sq))
-    a.delta = _f32(delta, "delta", bwd_stats_shape(B, H, Sq))
+    B, Sq, H, D = q.shape
+    a.dout = _t4(dout, "dout", q.dtype, (B, Sq, H, D), q)
+    a.lse = _f32(lse, "lse", (B, H, Sq), q)
+    a.delta = _f32(delta, "delta", bwd_stats_shape(B, H, Sq), q)
     a.delta_bytes = delta.numel() * 4
     return a
 
@@ -376,13 +410,14 @@ def attn_bwd_dq_block(q, k, v, dout, lse, delta, *, q_start=0, k_start=0, causal
     if final:
         if dq is None:
             dq = torch.empty((B, Sq, H, D), dtype=q.dtype, device=q.device)
-        a.dq = _t4(dq, "dq", q.dtype)
+        a.dq = _t4(dq, "dq", q.dtype, (B, Sq, H, D), q)
     elif dq_acc is None:
         dq_acc = torch.empty(_acc_shape(B, Sq, H, D, acc_head_major), dtype=torch.float32, device=q.device)
-    a.dq_acc = _f32(dq_acc, "dq_acc", _acc_shape(B, Sq, H, D, acc_head_major))
+    a.dq_acc = _f32(dq_acc, "dq_acc", _acc_shape(B, Sq, H, D, acc_head_major), q)
     a.dq_acc_head_major = int(bool(acc_head_major))
     a.carry_in = int(bool(carry_in))
     a.final_out = int(bool(final))
+    _set_hints(a)
     L = lib()
     _capi.check(L, _entry(L, "lwm_attn_bwd_dq", q.dtype)(C.byref(a), _stream_ptr()), "lwm_attn_bwd_dq")
     return dq if final else dq_acc
@@ -400,16 +435,17 @@ def attn_bwd_dkdv_block(q, k, v, dout, lse, delta, *, q_start=0, k_start=0, caus
             dk = torch.empty((B, Sk, H, D), dtype=q.dtype, device=q.device)
         if dv is None:
             dv = torch.empty((B, Sk, H, D), dtype=q.dtype, device=q.device)
-        a.dk, a.dv = _t4(dk, "dk", q.dtype), _t4(dv, "dv", q.dtype)
+        a.dk, a.dv = _t4(dk, "dk", q.dtype, (B, Sk, H, D), q), _t4(dv, "dv", q.dtype, (B, Sk, H, D), q)
     else:
         if dk_acc is None:
             dk_acc = torch.empty((B, Sk, H, D), dtype=torch.float32, device=q.device)
         if dv_acc is None:
             dv_acc = torch.empty((B, Sk, H, D), dtype=torch.float32, device=q.device)
-    a.dk_acc = _f32(dk_acc, "dk_acc", (B, Sk, H, D))
-    a.dv_acc = _f32(dv_acc, "dv_acc", (B, Sk, H, D))
+    a.dk_acc = _f32(dk_acc, "dk_acc", (B, Sk, H, D), q)
+    a.dv_acc = _f32(dv_acc, "dv_acc", (B, Sk, H, D), q)
     a.carry_in = int(bool(carry_in))
     a.final_out = int(bool(final))
+    _set_hints(a)
     L = lib()
     _capi.check(L, _entry(L, "lwm_attn_bwd_dkdv", q.dtype)(C.byref(a), _stream_ptr()), "lwm_attn_bwd_dkdv")
     return (dk, dv) if final else (dk_acc, dv_acc)
@@ -420,6 +456,8 @@ def cast_f32_to_bf16(src, dst=None):
         raise ValueError("cast_f32_to_bf16: expected contiguous f32 device tensor")
     if dst is None:
         dst = torch.empty(src.shape, dtype=torch.bfloat16, device=src.device)
+    elif dst.device != src.device or dst.dtype != torch.bfloat16 or not dst.is_contiguous() or dst.numel() != src.numel():
+        raise ValueError(f"cast_f32_to_bf16: dst must be a contiguous bf16 tensor of {src.numel()} elements on {src.device}")
     L = lib()
     _capi.check(L, L.lwm_cast_f32_to_bf16(src.data_ptr(), dst.data_ptr(), src.numel(),
                                           _stream_ptr()), "lwm_cast_f32_to_bf16")
@@ -429,12 +467,16 @@ def cast_f32_to_bf16(src, dst=None):
 def sum_f32_to_bf16(srcs, dst=None):
     """bf16(((srcs[0] + srcs[1]) + ...)) -- the owner-side reduction of returned dK/dV partials."""
     srcs = list(srcs)
+    if not srcs:
+        raise ValueError("sum_f32_to_bf16: expected at least one source")
     for s in srcs:
-        if not s.is_cuda or s.dtype != torch.float32 or not s.is_contiguous() or s.shape != srcs[0].shape:
-            raise ValueError("sum_f32_to_bf16: expected same-shaped contiguous f32 device tensors")
+        if not s.is_cuda or s.dtype != torch.float32 or not s.is_contiguous() or s.shape != srcs[0].shape or \
+                s.device != srcs[0].device:
+            raise ValueError("sum_f32_to_bf16: expected same-shaped contiguous f32 tensors on one device")
     if dst is None:
         dst = torch.empty(srcs[0].shape, dtype=torch.bfloat16, device=srcs[0].device)
-    elif not dst.is_contiguous() or dst.dtype not in (torch.bfloat16, torch.float32) or dst.numel() != srcs[0].numel():
+    elif dst.device != srcs[0].device or not dst.is_contiguous() or dst.dtype not in (torch.bfloat16, torch.float32) or \
+            dst.numel() != srcs[0].numel():
         raise ValueError("sum_f32_to_bf16: dst must be a contiguous bf16 (or, the fp32 flavour, f32) tensor of the same size")
     ptrs = (C.c_void_p * len(srcs))(*[s.data_ptr() for s in srcs])
     L = lib()
@@ -447,9 +489,13 @@ def sum_f32_to_bf16(srcs, dst=None):
 
 
 # ---------------------------------------------------------------- VQGAN primitives
-def _f32c(t, name):
+def _f32c(t, name, shape=None, like=None):
     if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
         raise ValueError(f"{name}: expected a contiguous f32 ROCm device tensor (lwm_amd has no CPU path)")
+    if like is not None and t.device != like.device:
+        raise ValueError(f"{name}: expected a tensor on {like.device}, got {t.device}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
     return t.data_ptr()
 
 
@@ -458,6 +504,8 @@ def conv2d_nhwc(x, w, bias=None, residual=None, *, stride=1, pad=None, up_shift=
     """flax nn.Conv on NHWC f32 (lwm_conv2d_nhwc_f32).  x (B,H,W,Cin), w (KH,KW,Cin,Cout) HWIO.
     pad=None = 'SAME' for stride 1.  Downsample: stride=2, pad=0, out_hw=(H//2, W//2);
     Upsample+conv: up_shift=1."""
+    if x.dim() != 4 or w.dim() != 4:
+        raise ValueError("conv2d_nhwc: x must be (B,H,W,Cin) and w (KH,KW,Cin,Cout)")
     B, Hin, Win, Cin = x.shape
     KH, KW, Cin2, Cout = w.shape
     if Cin2 != Cin:
@@ -472,10 +520,10 @@ def conv2d_nhwc(x, w, bias=None, residual=None, *, stride=1, pad=None, up_shift=
         out = torch.empty((B, Ho, Wo, Cout), dtype=torch.float32, device=x.device)
     if residual is not None and tuple(residual.shape) != tuple(out.shape):
         raise ValueError("conv2d_nhwc: residual shape mismatch")
-    a = _capi.LwmConvArgs(_f32c(x, "x"), _f32c(w, "w"),
-                          None if bias is None else _f32c(bias, "bias"),
-                          None if residual is None else _f32c(residual, "residual"),
-                          _f32c(out, "out"), B, Hin, Win, Cin, Cout, KH, KW, stride, pad, up_shift,
+    a = _capi.LwmConvArgs(_f32c(x, "x"), _f32c(w, "w", like=x),
+                          None if bias is None else _f32c(bias, "bias", (Cout,), x),
+                          None if residual is None else _f32c(residual, "residual", like=x),
+                          _f32c(out, "out", (B, Ho, Wo, Cout), x), B, Hin, Win, Cin, Cout, KH, KW, stride, pad, up_shift,
                           Ho, Wo, int(bool(clip)))
     L = lib()
     _capi.check(L, L.lwm_conv2d_nhwc_f32(C.byref(a), _stream_ptr()), "lwm_conv2d_nhwc_f32")
@@ -488,24 +536,33 @@ def groupnorm_silu(x, gamma, beta, *, groups=32, eps=1e-6, silu=True, out=None, 
     HW = x.numel() // (B * Cc) if B else 0
     if gamma.numel() != Cc or beta.numel() != Cc:
         raise ValueError(f"groupnorm_silu: scale/bias have {gamma.numel()}/{beta.numel()} elements, x has {Cc} channels")
+    if groups < 1 or Cc % groups:
+        raise ValueError(f"groupnorm_silu: {Cc} channels do not split into {groups} groups")
+    px, pg, pb = _f32c(x, "x"), _f32c(gamma, "gamma", like=x), _f32c(beta, "beta", like=x)
+    if out is not None:
+        _f32c(out, "out", x.shape, x)
+    if workspace is not None and workspace.device != x.device:
+        raise ValueError(f"workspace: expected a tensor on {x.device}")
     L = lib()
     need = L.lwm_groupnorm_workspace_bytes(B, HW, Cc, groups)
     if workspace is None or workspace.numel() * workspace.element_size() < need:
         workspace = torch.empty((max(need, 16) + 7) // 8, dtype=torch.float64, device=x.device)
     if out is None:
         out = torch.empty_like(x)
-    _capi.check(L, L.lwm_groupnorm_silu_f32(_f32c(x, "x"), _f32c(gamma, "gamma"), _f32c(beta, "beta"),
-                                            _f32c(out, "out"), workspace.data_ptr(), B, HW, Cc, groups,
+    _capi.check(L, L.lwm_groupnorm_silu_f32(px, pg, pb, out.data_ptr(), workspace.data_ptr(), B, HW, Cc, groups,
                                             float(eps), int(bool(silu)), _stream_ptr()),
                 "lwm_groupnorm_silu_f32")
     return out
 
 
 def vq_sqnorm(codebook):
+    if codebook.dim() != 2:
+        raise ValueError("codebook: expected a contiguous f32 (E, D) device tensor")
     E, D = codebook.shape
+    pc = _f32c(codebook, "codebook")
     se = torch.empty(E, dtype=torch.float32, device=codebook.device)
     L = lib()
-    _capi.check(L, L.lwm_vq_sqnorm_f32(_f32c(codebook, "codebook"), se.data_ptr(), E, D, _stream_ptr()),
+    _capi.check(L, L.lwm_vq_sqnorm_f32(pc, se.data_ptr(), E, D, _stream_ptr()),
                 "lwm_vq_sqnorm_f32")
     return se
 
@@ -518,21 +575,23 @@ def vq_argmin(z, codebook, se=None):
     if se is None:
         se = vq_sqnorm(codebook)
     N = z.numel() // D
+    pz, pc, ps = _f32c(z, "z"), _f32c(codebook, "codebook", like=z), _f32c(se, "se", (E,), z)
     idx = torch.empty(z.shape[:-1], dtype=torch.int32, device=z.device)
     L = lib()
-    _capi.check(L, L.lwm_vq_argmin_f32(_f32c(z, "z"), _f32c(codebook, "codebook"), _f32c(se, "se"),
+    _capi.check(L, L.lwm_vq_argmin_f32(pz, pc, ps,
                                        idx.data_ptr(), N, E, D, _stream_ptr()), "lwm_vq_argmin_f32")
     return idx
 
 
 def vq_gather(codebook, idx, z=None):
     E, D = codebook.shape
-    if idx.dtype != torch.int32 or not idx.is_contiguous() or not idx.is_cuda:
-        raise ValueError("vq_gather: idx must be a contiguous int32 device tensor")
+    pc = _f32c(codebook, "codebook")
+    if idx.dtype != torch.int32 or not idx.is_contiguous() or idx.device != codebook.device:
+        raise ValueError("vq_gather: idx must be a contiguous int32 tensor on the codebook's device")
+    pz = None if z is None else _f32c(z, "z", tuple(idx.shape) + (D,), codebook)
     out = torch.empty(tuple(idx.shape) + (D,), dtype=torch.float32, device=codebook.device)
     L = lib()
-    _capi.check(L, L.lwm_vq_gather_f32(_f32c(codebook, "codebook"), idx.data_ptr(),
-                                       None if z is None else _f32c(z, "z"), out.data_ptr(),
+    _capi.check(L, L.lwm_vq_gather_f32(pc, idx.data_ptr(), pz, out.data_ptr(),
                                        idx.numel(), E, D, _stream_ptr()), "lwm_vq_gather_f32")
     return out
 

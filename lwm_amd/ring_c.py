@@ -270,18 +270,23 @@ class CRing:
                              f"needs ipc_slots >= {need}")
         B, c, H, D = q.shape
         a = _capi.LwmRingArgs()
-        a.q, a.k, a.v, a.out = _t4(q, "q"), _t4(k, "k"), _t4(v, "v"), _t4(out, "out")
+        a.q, a.k, a.v, a.out = (_t4(q, "q"), _t4(k, "k", q.dtype, (B, c, H, D), q), _t4(v, "v", q.dtype, (B, c, H, D), q),
+                                _t4(out, "out", q.dtype, (B, c, H, D), q))
+        if lse.device != q.device or lse.dtype != torch.float32 or tuple(lse.shape) != (B, H, c) or not lse.is_contiguous():
+            raise ValueError(f"lse: expected a contiguous f32 {(B, H, c)} tensor on {q.device}")
         a.lse = lse.data_ptr()
         a.B, a.c, a.H, a.D = B, c, H, D
         a.scale = float(scale) if scale is not None else 1.0 / D ** 0.5
         a.causal = int(bool(causal))
         Sg = c * self.size
         if segment_ids is not None:
-            if segment_ids.dtype != torch.int32 or tuple(segment_ids.shape) != (B, Sg) or not segment_ids.is_contiguous():
+            if segment_ids.dtype != torch.int32 or tuple(segment_ids.shape) != (B, Sg) or not segment_ids.is_contiguous() or \
+                    segment_ids.device != q.device:
                 raise ValueError(f"segment_ids: expected contiguous int32 {(B, Sg)} (replicated, full length)")
             a.segment_ids = segment_ids.data_ptr()
         if key_valid is not None:
-            if key_valid.dtype != torch.uint8 or tuple(key_valid.shape) != (B, Sg) or not key_valid.is_contiguous():
+            if key_valid.dtype != torch.uint8 or tuple(key_valid.shape) != (B, Sg) or not key_valid.is_contiguous() or \
+                    key_valid.device != q.device:
                 raise ValueError(f"key_valid: expected contiguous uint8 {(B, Sg)} (replicated, full length)")
             a.key_valid = key_valid.data_ptr()
         a.workspace = self._workspace(B, c, H, D, backward)
@@ -348,7 +353,7 @@ class CRing:
         a = self._args(q, k, v, out, lse, segment_ids, key_valid, scale, causal, True, layout)
         if kv_keep is not None:
             a.kv_keep, a.kv_kept = kv_keep.data_ptr(), 1
-        a.dout, a.dq, a.dk, a.dv = _t4(dout, "dout"), _t4(dq, "dq"), _t4(dk, "dk"), _t4(dv, "dv")
+        a.dout, a.dq, a.dk, a.dv = _t4(dout, "dout", q.dtype, (B, c, H, D), q), _t4(dq, "dq"), _t4(dk, "dk"), _t4(dv, "dv")
         L = lib()
         with self._guard("backward"):
             _capi.check(L, L.lwm_ring_attn_bwd(self._h, C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream)),

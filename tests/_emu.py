@@ -267,6 +267,31 @@ def attn_bwd_f32(q, k, v, out, lse, dout, *, causal=True, q_start=0, k_start=0, 
     return (dq, dk, dv) if final else (dq_acc, dk_acc, dv_acc)
 
 
+# ---------------------------------------------------------------- caller-owned (possibly strided) operands
+def attn_train_raw(q, k, v, out, dout, dq, dk, dv, *, causal=True, q_start=0, k_start=0, seg_q=None, seg_k=None,
+                   key_valid=None, scale=None):
+    """Forward + backward IN PLACE on the caller's arrays: uint16 (bf16 bits) -- or float32, the fp32 flavour -- (B,S,H,D)
+    views with any strides the ABI takes (last dimension contiguous, 16-byte aligned rows).  out, dq, dk, dv are written
+    through their own strides; returns lse (B,H,Sq)."""
+    L = lib()
+    f32 = q.dtype == np.float32
+    t4 = _t4f if f32 else _t4
+    B, Sq, H, D = q.shape
+    kw = dict(causal=causal, q_start=q_start, k_start=k_start, seg_q=seg_q, seg_k=seg_k, key_valid=key_valid, scale=scale)
+    a, keep = _base_args_f32(q, k, v, **kw) if f32 else base_args(q, k, v, **kw)
+    lse = aligned((B, H, Sq), np.float32)
+    lse[...] = np.nan
+    delta = aligned((L.lwm_attn_bwd_delta_bytes(B, H, Sq) // 4,), np.float32)
+    delta[...] = np.nan
+    a.out, a.dout, a.dq, a.dk, a.dv = t4(out), t4(dout), t4(dq), t4(dk), t4(dv)
+    a.lse, a.delta, a.delta_bytes = lse.ctypes.data, delta.ctypes.data, delta.nbytes
+    a.final_out = 1
+    sfx = "_f32" if f32 else ""
+    for name in ("lwm_attn_fwd", "lwm_attn_bwd_delta", "lwm_attn_bwd_dkdv", "lwm_attn_bwd_dq"):
+        _capi.check(L, getattr(L, name + sfx)(C.byref(a), None), name + sfx)
+    return lse
+
+
 # ---------------------------------------------------------------- VQGAN primitives
 def _af32(x):
     a = aligned(np.shape(x), np.float32)

@@ -43,8 +43,8 @@ def emu_cache(B, S, H):
     return _emu.aligned((B, S, H, 128), np.uint8), _emu.aligned((B, S, H), np.float32)
 
 
-def emu_decode(q, kq, ks, vq, vs, mask, k_splits):
-    """-> (out f32 (B,1,H,128), lse (B,H,1)) through lwm_attn_decode_kv8 + lwm_attn_combine"""
+def emu_decode(q, kq, ks, vq, vs, mask, k_splits, scale=None):
+    """-> (out f32 (B,1,H,128), lse (B,H,1)) through lwm_attn_decode_kv8 + lwm_attn_combine; scale: default 1/sqrt(D)"""
     L = _emu.lib()
     B, _, H, D = q.shape
     Sk = kq.shape[1]
@@ -59,7 +59,7 @@ def emu_decode(q, kq, ks, vq, vs, mask, k_splits):
     if mask is not None:
         mask = np.ascontiguousarray(mask.reshape(B, Sk).astype(np.uint8))
         a.dense_mask, a.mask_stride_b = mask.ctypes.data, Sk
-    a.B, a.Sk, a.H, a.D, a.scale, a.k_splits = B, Sk, H, D, 1.0 / np.sqrt(D), k_splits
+    a.B, a.Sk, a.H, a.D, a.scale, a.k_splits = B, Sk, H, D, (1.0 / np.sqrt(D) if scale is None else scale), k_splits
     P = max(1, k_splits)
     op, lp = _emu.aligned((P, B, 1, H, D), np.float32), _emu.aligned((P, B, H, 1), np.float32)
     a.out_acc, a.lse_acc = op.ctypes.data, lp.ctypes.data
