@@ -745,57 +745,91 @@ LWM_KERNEL(kD4Threads) void attn_bwd_dkdv4_meta_kernel(AttnParams p) { attn_bwd_
 // file header): p from the saved LSE, dp = do v^T, ds = p * (dp - delta), dq += ds k * scale.  Same contract,
 // operands, masks, carries and segment-block hints as the dK/dV kernel above.
 //
-// Workgroup = 4 waves = 128 queries; a wave owns 32 query rows: their Q and dO fragments (B operands, 32 + 32
-// registers) and the f32 dQ^T accumulator (64) live in the accumulator file.  Everything is computed transposed, as
-// in the forward: a lane owns one query column, so the row statistics are two scalars per lane and -delta, the initial
-// value of the dP chain, is ONE constant tuple for the whole launch (no per-unit statistics traffic at all).  K / V
-// arrive by LDS-DMA in steps of 64 keys through the same ring of four 32-KiB slots [K tile | V tile]; a unit = 32 keys:
+// Matrix instruction: v_mfma_f32_16x16x32_bf16 (the dK/dV kernel and the forward use 32x32x16).  At its power limit
+// the chip holds a higher clock on this shape -- same FLOP, same cycles per FLOP, 7 - 18 % more FLOP/s on random
+// operands (profiles/r09_dq16.md) -- so the unit below is the old one cut into 16 x 16 tiles at the same bytes and
+// registers.  Operand maps (lane l: c = l & 15, g = l >> 4): A holds row c, k = 8g .. 8g+7; B holds column c, the same
+// k; C / D hold column c, rows 4g .. 4g+3.
 //
-//   phase   matrix pipe                                                   vector pipe (same wave)
-//   X(u)    S^T(u) = K(u) Q^T  and  dP'^T(u) = V(u) dO^T - delta, 16      the vector work of unit u-1 continues
-//   Y(u)    dQ^T += K(u-1)^T dS^T(u-1), 8 MFMAs over 4 tuples             t = S c - lse2, p = exp2(t), dS = p dP' -> bf16
+// Workgroup = 4 waves = 128 queries; a wave owns 32 query rows = two halves qh of 16: their Q and dO fragments (B
+// operands, 32 + 32 registers) and the f32 dQ^T accumulator (64) live in the accumulator file.  Everything is computed
+// transposed, as in the forward: a lane owns query column c of each half, so the row statistics are two scalars per
+// lane and half, and -delta, the initial value of the dP chains, is ONE constant tuple per half for the whole launch
+// (no per-unit statistics traffic at all).  K / V arrive by LDS-DMA in steps of 64 keys through the same ring of four
+// 32-KiB slots [K tile | V tile]; a unit = 32 keys = two halves kh of 16:
 //
-// S and dP' have two register tiles each (by unit parity): the 56 VALU of a unit spread over the 24 gaps of Y(u) and
-// X(u+1).  With key meta (segment ids, padded keys, a ragged last tile) the 64 meta words of a step are staged through
-// LDS by the threads themselves, as the forward does.
+//   phase   matrix pipe                                                     vector pipe (same wave)
+//   X(u)    S^T(u)[kh][qh] = K(u) Q^T and dP'^T(u) = V(u) dO^T - delta:     the vector work of unit u-1 continues
+//           16 row fragments (ds_read_b128), each feeds the two qh: 32
+//   Y(u)    dQ^T[db < 8][qh] += K(u-1)^T(db) dS^T(u-1)[qh]: 8 transposed    t = S c - lse2, p = exp2(t), dS = p dP' -> bf16
+//           fragments (2 x ds_read_b64_tr_b16), each feeds the two qh: 16
+//
+// The B operand of Y is the packed dS of the subtiles (kh = 0, qh) | (kh = 1, qh) as the MFMAs left them, which puts
+// k-group g at keys {4g .. 4g+3, 16+4g .. 16+4g+3}: the transposed read takes its first four keys from rows 4g .., its
+// second four from rows 16+4g ...  S and dP' have two sets of register tiles (by unit parity): the 56 VALU of a unit
+// spread over the 48 gaps of Y(u) and X(u+1).  With key meta (segment ids, padded keys, a ragged last tile) the 64 meta
+// words of a step are staged through LDS by the threads themselves, as the forward does.
 //
 // LDS map: slot 0..3 = [K tile 64 rows | V tile 64 rows] (16 KiB each) | key meta 0..3 (64 words each)
+// Tile image: 256-byte rows, slot s of row r at physical slot s ^ q4_swz(r).  The swizzle of attn_common.h would leave
+// both reads of this operand shape 2-way (the b128 lane groups take rows 0-3, 12-15 at one slot and rows 4-11 at its
+// neighbour; a half-wave of the transposed read takes 8 consecutive rows x 32 bytes); this one has
+//   * q4_swz(r) ^ [4 <= r&15 < 12] a bijection of r & 15      -> the row reads are conflict-free,
+//   * q4_swz(r) >> 1 a bijection of r & 7                     -> the transposed reads are conflict-free.
 constexpr int kQ4BQ = 128;      // queries per workgroup
 constexpr int kQ4BK = 64;       // keys per step (two units of 32)
 constexpr int kQ4OffMeta = kD4Slots * kD4SlotBytes;
 constexpr int kQ4LdsBytes = kQ4OffMeta + kD4Slots * kQ4BK * 4;
 
-// G = 0..7 = the gaps of Y(u), G = 8..23 = the gaps of X(u+1).  F >= 1; E behind F, M behind E, D behind its two M; the
-// product of Y(u) still reads the OLD dS words: the first half (i < 4) may be rewritten from G = 4, the second from G = 8;
-// everything done by G = 21.
+LWM_DEVICE int q4_swz(int row) {
+    const int r = row & 15;
+    return (((r & 7) << 1) | (r >> 3)) ^ ((r >= 4 && r < 12) ? 1 : 0);
+}
+LWM_DEVICE uint32_t q4_tile_off(int row, int slot) { return (uint32_t)(row * kRowBytes + ((slot ^ q4_swz(row)) << 4)); }
+
+// G = 0..15 = the gaps of Y(u), G = 16..47 = the gaps of X(u+1) (gap = behind that MFMA).  An MFMA holds the vector
+// issue for 8 of its 16 cycles, so a gap takes two plain VALU or one v_exp_f32 beside its LDS read.  F >= 3 (three
+// MFMAs between the end of the S chains and their first reader); E behind F, M behind E, D behind its two M; the
+// products of Y(u) read the OLD dS words to their last MFMA: D >= 16; everything done by G = 45.
 struct Q4Sched {
     int F[16], E[16], M[16], D[8];
 };
 constexpr bool q4_sched_ok(const Q4Sched& c) {
-    for (int e = 0; e < 16; ++e)
-        if (c.F[e] < 1 || c.E[e] <= c.F[e] || c.M[e] <= c.E[e] || c.M[e] > 21) return false;
-    for (int i = 0; i < 8; ++i)
-        if (c.D[i] < (i < 4 ? 4 : 8) || c.D[i] > 21 || c.D[i] <= c.M[2 * i] || c.D[i] <= c.M[2 * i + 1]) return false;
+    int load[48] = {};
+    for (int e = 0; e < 16; ++e) {
+        if (c.F[e] < 3 || c.E[e] <= c.F[e] || c.M[e] <= c.E[e] || c.M[e] > 45) return false;
+        load[c.F[e]] += 1;
+        load[c.E[e]] += 2;
+        load[c.M[e]] += 1;
+    }
+    for (int i = 0; i < 8; ++i) {
+        if (c.D[i] < 16 || c.D[i] > 45 || c.D[i] <= c.M[2 * i] || c.D[i] <= c.M[2 * i + 1]) return false;
+        load[c.D[i]] += 1;
+    }
+    for (int g = 0; g < 48; ++g)
+        if (load[g] > 2) return false;      // (in units of a plain VALU's issue; an exp counts two)
     return true;
 }
-constexpr Q4Sched kQ4Sched = {      // two per gap beside the transposed reads of Y, three beside the row reads of X
-    /* F */ {1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8},
-    /* E */ {8, 9, 9, 9, 10, 10, 10, 11, 11, 11, 12, 12, 12, 13, 13, 13},
-    /* M */ {14, 14, 14, 15, 15, 15, 16, 16, 16, 17, 17, 17, 18, 18, 18, 19},
-    /* D */ {19, 19, 20, 20, 20, 21, 21, 21}};
-static_assert(q4_sched_ok(kQ4Sched), "filler schedule violates a dependency");
+constexpr Q4Sched kQ4Sched = {
+    /* F */ {3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 13, 14, 14, 15, 15},
+    /* E */ {16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31},
+    /* M */ {32, 32, 33, 33, 34, 34, 35, 35, 36, 36, 37, 37, 38, 38, 39, 39},
+    /* D */ {40, 40, 41, 41, 42, 42, 43, 43}};
+static_assert(q4_sched_ok(kQ4Sched), "filler schedule violates a dependency or the issue budget of a gap");
 
 struct Q4Ctx {
-    uint32_t ka[8];             // K row-fragment addresses (d step s), rows 0..31 of the CURRENT step's K tile
-    uint32_t tlo[4], tup[4];    // K transposed-fragment addresses (d block), rows 0..15 of the current step's K tile
-    uint32_t plo[4], pup[4];    // the same in the PREVIOUS step's slot
-    uint32_t meta;              // this step's key meta + 16 * hi
-    float c, nl;                // scale * log2(e); -lse * log2(e) of this lane's query (-inf: p = 0)
+    uint32_t ka[4];             // K row-fragment addresses (d step s of 32), rows 0..15 of the CURRENT step's K tile
+    uint32_t tlo[8];            // K transposed-fragment addresses (d block of 16), rows 4g.. of the current step's K tile
+    uint32_t plo[8];            // the same in the PREVIOUS step's slot
+    uint32_t meta;              // this step's key meta + 16 * g
+    float c, nl[2];             // scale * log2(e); -lse * log2(e) of this lane's two queries (-inf: p = 0)
 };
 
+// element e of the vector work = (qh = e >> 3, kh = (e >> 2) & 1, j = e & 3): score tile e >> 2 = 2 qh + kh, register j;
+// the dS words of a query half are then four consecutive packed registers, ready as the B operand of Y
 struct Q4Regs {
-    f32x16 s[2], dp[2];         // S^T / dP'^T tiles by unit parity (MFMA results, read-only for the vector pipe)
-    f32x16 ndl;                 // -delta of this lane's query in every element: the C operand that starts each dP chain
+    f32x4 s[2][4], dp[2][4];    // S^T / dP'^T tiles by unit parity (MFMA results, read-only for the vector pipe)
+    f32x4 ndl[2];               // -delta of this lane's queries in every element: the C operand that starts each dP chain
     float t[16], ds[16];
     bf16x8 dsb[2];
     uint32_t dw[8];
@@ -803,34 +837,77 @@ struct Q4Regs {
 };
 
 #ifdef LWM_EMU
-LWM_DEVICE void q4_mfma_c_first(f32x16& d, bf16x8 a, bf16x8 b, const f32x16& c) { d = mfma_32x32x16(a, b, c); }
-LWM_DEVICE void q4_opaque(f32x16&) {}
-#else
-// first MFMA of a dP chain: C = the -delta tuple (two wait states in front, see d4_mfma_p_first)
-LWM_DEVICE void q4_mfma_c_first(f32x16& d, bf16x8 a, bf16x8 b, const f32x16& c) {
-    asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %3" : "=&v"(d) : "v"(a), "a"(b), "v"(c));
+// host form of v_mfma_f32_16x16x32_bf16 from its operand maps (scripts/micro/mfma_timing.hip prints the device's;
+// tests/test_gpu_dq16.py holds the device kernel to the oracle the emulated one meets)
+LWM_DEVICE f32x4 mfma_16x16x32(bf16x8 a, bf16x8 b, f32x4 c) {
+    emu::Wave& w = emu::g_blk->waves[emu::g_lane->tid >> 6];
+    const int l = emu::g_lane->tid & 63;
+    w.a[l] = a;
+    w.b[l] = b;
+    emu::wave_sync();
+    f32x4 d;
+    const int col = l & 15, g = l >> 4;
+    for (int j = 0; j < 4; ++j) {
+        const int row = 4 * g + j;
+        float s = c[j];
+        for (int k = 0; k < 32; ++k) s += (float)w.a[(k >> 3) * 16 + row][k & 7] * (float)w.b[(k >> 3) * 16 + col][k & 7];
+        d[j] = s;
+    }
+    emu::wave_sync();
+    return d;
 }
-// sixteen registers that hold the same value: hipcc must not know (it would keep one and copy it into a tuple in
-// front of every chain)
-LWM_DEVICE void q4_opaque(f32x16& x) { asm volatile("" : "+v"(x)); }
+LWM_DEVICE void q4_mfma_first(f32x4& d, bf16x8 a, bf16x8 b) { d = mfma_16x16x32(a, b, f32x4{0.0f, 0.0f, 0.0f, 0.0f}); }
+LWM_DEVICE void q4_mfma(f32x4& d, bf16x8 a, bf16x8 b) { d = mfma_16x16x32(a, b, d); }
+LWM_DEVICE void q4_mfma_c_first(f32x4& d, bf16x8 a, bf16x8 b, const f32x4& c) { d = mfma_16x16x32(a, b, c); }
+LWM_DEVICE void q4_mfma_o(f32x4& d, bf16x8 a, bf16x8 b) { d = mfma_16x16x32(a, b, d); }
+LWM_DEVICE void q4_mfma_o_first(f32x4& d, bf16x8 a, bf16x8 b) { d = mfma_16x16x32(a, b, f32x4{0.0f, 0.0f, 0.0f, 0.0f}); }
+LWM_DEVICE void q4_opaque(f32x4 (&)[2]) {}
+LWM_DEVICE void q4_settle_t(f32x4 (&)[4]) {}
+LWM_DEVICE void q4_settle_acc(f32x4 (&)[16]) {}
+#else
+// the statements of attn_fwd64.h / d4_mfma_* above on the 16x16 shape: S chains (B from the accumulator file), the
+// first MFMA of a dP chain (C = the -delta tuple, two wait states in front, see d4_mfma_p_first), dQ^T products
+LWM_DEVICE void q4_mfma_first(f32x4& d, bf16x8 a, bf16x8 b) {
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&v"(d) : "v"(a), "a"(b));
+}
+LWM_DEVICE void q4_mfma(f32x4& d, bf16x8 a, bf16x8 b) {
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "a"(b));
+}
+LWM_DEVICE void q4_mfma_c_first(f32x4& d, bf16x8 a, bf16x8 b, const f32x4& c) {
+    asm volatile("s_nop 1\n\tv_mfma_f32_16x16x32_bf16 %0, %1, %2, %3" : "=&v"(d) : "v"(a), "a"(b), "v"(c));
+}
+LWM_DEVICE void q4_mfma_o(f32x4& d, bf16x8 a, bf16x8 b) {
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(d) : "v"(a), "v"(b));
+}
+LWM_DEVICE void q4_mfma_o_first(f32x4& d, bf16x8 a, bf16x8 b) {
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&a"(d) : "v"(a), "v"(b));
+}
+// registers that hold the same value: hipcc must not know (it would keep one and copy it into a tuple in front of
+// every chain)
+LWM_DEVICE void q4_opaque(f32x4 (&x)[2]) { asm volatile("" : "+v"(x[0]), "+v"(x[1])); }
+LWM_DEVICE void q4_settle_t(f32x4 (&s)[4]) { asm volatile("s_nop 7\n\ts_nop 7" : "+v"(s[0]), "+v"(s[1]), "+v"(s[2]), "+v"(s[3])); }
+LWM_DEVICE void q4_settle_acc(f32x4 (&a)[16]) {
+    asm volatile("s_nop 7\n\ts_nop 7"
+                 : "+a"(a[0]), "+a"(a[1]), "+a"(a[2]), "+a"(a[3]), "+a"(a[4]), "+a"(a[5]), "+a"(a[6]), "+a"(a[7]), "+a"(a[8]),
+                   "+a"(a[9]), "+a"(a[10]), "+a"(a[11]), "+a"(a[12]), "+a"(a[13]), "+a"(a[14]), "+a"(a[15]));
+}
 #endif
 
-// fragment f of a unit (MFMA index 0..23; 24.. = the first fragments of the unit that follows):
-//   0..15   phase X: d step f>>1; even = K row fragment (S^T), odd = V row fragment (dP'^T)
-//   16..23  phase Y: K^T of the PREVIOUS unit, (key step (f>>2)&1, d block f&3)
+// fragment f of a unit (24 per unit, each feeds the MFMAs of the two query halves; 24.. = the first fragments of the
+// unit that follows):
+//   0..15   phase X: pair f>>1 = (d step s = f>>2, key half kh = (f>>1)&1); even = K row fragment (S^T), odd = V (dP'^T)
+//   16..23  phase Y: K^T of the PREVIOUS unit, d block f-16: keys 4g.. (first read) and 16+4g.. (second read)
 template <int HALF>
 LWM_DEVICE bf16x8 q4_frag(const Q4Ctx& cx, int f) {
     if (f >= 24) {
         const int g = f - 24;
-        return lds_read_b128(cx.ka[g >> 1] + (g & 1) * kD4TileBytes + (HALF == 0 ? 32 * kRowBytes : 0));
+        return lds_read_b128(cx.ka[g >> 2] + (g & 1) * kD4TileBytes + ((g >> 1) & 1) * 16 * kRowBytes + (HALF == 0 ? 32 * kRowBytes : 0));
     }
-    if (f < 16) return lds_read_b128(cx.ka[f >> 1] + (f & 1) * kD4TileBytes + HALF * 32 * kRowBytes);
-    const int j = f - 16, t = (j >> 2) & 1, db = j & 3;
-    const uint32_t alo = HALF == 0 ? cx.plo[db] : cx.tlo[db];
-    const uint32_t aup = HALF == 0 ? cx.pup[db] : cx.tup[db];
-    const uint32_t off = (HALF == 0 ? 32 * kRowBytes : 0) + 16 * t * kRowBytes;
-    bf16x4 lo = lds_read_tr16(alo + off);
-    bf16x4 up = lds_read_tr16(aup + off);
+    if (f < 16) return lds_read_b128(cx.ka[f >> 2] + (f & 1) * kD4TileBytes + ((f >> 1) & 1) * 16 * kRowBytes + HALF * 32 * kRowBytes);
+    const int db = f - 16;
+    const uint32_t a = (HALF == 0 ? cx.plo[db] : cx.tlo[db]) + (HALF == 0 ? 32 * kRowBytes : 0);
+    bf16x4 lo = lds_read_tr16(a);
+    bf16x4 up = lds_read_tr16(a + 16 * kRowBytes);
     bf16x8 o;
     o[0] = lo[0]; o[1] = lo[1]; o[2] = lo[2]; o[3] = lo[3];
     o[4] = up[0]; o[5] = up[1]; o[6] = up[2]; o[7] = up[3];
@@ -842,9 +919,9 @@ template <int G, int PAR>
 LWM_DEVICE void q4_fillers(const Q4Ctx& cx, Q4Regs& rg) {
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-        if (kQ4Sched.F[e] == G) rg.t[e] = f4_fma(rg.s[PAR][e], cx.c, cx.nl);
+        if (kQ4Sched.F[e] == G) rg.t[e] = f4_fma(rg.s[PAR][e >> 2][e & 3], cx.c, cx.nl[e >> 3]);
         if (kQ4Sched.E[e] == G) rg.t[e] = f4_exp2(rg.t[e]);
-        if (kQ4Sched.M[e] == G) rg.ds[e] = d4_mul(rg.t[e], rg.dp[PAR][e]);
+        if (kQ4Sched.M[e] == G) rg.ds[e] = d4_mul(rg.t[e], rg.dp[PAR][e >> 2][e & 3]);
     }
 #pragma unroll
     for (int i = 0; i < 8; ++i)
@@ -856,98 +933,111 @@ LWM_DEVICE void q4_fillers(const Q4Ctx& cx, Q4Regs& rg) {
         if (ld == G) rg.dsb[h] = __builtin_bit_cast(bf16x8, u32x4{rg.dw[4 * h], rg.dw[4 * h + 1], rg.dw[4 * h + 2], rg.dw[4 * h + 3]});
     }
 }
-template <int G0, int N, int PAR>
-LWM_DEVICE void q4_fill_at(int g, const Q4Ctx& cx, Q4Regs& rg) {
-    if constexpr (N > 0) {
-        if (g == G0) q4_fillers<G0, PAR>(cx, rg);
-        else q4_fill_at<G0 + 1, N - 1, PAR>(g, cx, rg);
-    }
-}
-
-// Phase X of unit u (parity HALF): the two chains alternating, fragments requested and consumed in pairs (attn d4_x);
-// fillers: gaps 8..23 of unit u-1.
-template <int HALF, bool HAS_PREV, bool DMA>
+// Every MFMA index below is a template parameter (the phases are recursions, not loops): fragment, tile and filler
+// selection must be constants, or the register arrays they index go to scratch.
+//
+// Phase X of unit u (parity HALF): 32 MFMAs, fragment m>>1 (pairs K | V requested together every fourth gap, the pair's
+// YOUNGER fragment consumed first: one wait per four MFMAs), query half m&1; fillers: gaps 16..47 of unit u-1.
+template <int HALF, bool HAS_PREV, bool DMA, int M = 0>
 LWM_DEVICE void q4_x(const Q4Ctx& cx, Q4Regs& rg, const bf16x8 (&qf)[8], const bf16x8 (&dof)[8], const uint32_t (&vk)[4],
                      const uint32_t (&vv)[4], const D4Dma& dm) {
-#pragma unroll
-    for (int m = 0; m < 16; ++m) {
-        if ((m & 1) == 0) {
-            rg.fr[(m + kD4Ahead) & 7] = q4_frag<HALF>(cx, m + kD4Ahead);
-            rg.fr[(m + kD4Ahead + 1) & 7] = q4_frag<HALF>(cx, m + kD4Ahead + 1);
+    if constexpr (M < 32) {
+        if constexpr ((M & 3) == 0) {
+            constexpr int f0 = (M >> 1) + kD4Ahead;
+            rg.fr[f0 & 7] = q4_frag<HALF>(cx, f0);
+            sched_fence();      // (the pair in this order: the wait for the younger fragment then covers both)
+            rg.fr[(f0 + 1) & 7] = q4_frag<HALF>(cx, f0 + 1);
         }
         sched_fence();
         {
-            const int f = m ^ 1;      // even = K (S^T), odd = V (dP'^T)
-            if (f == 0) f4_mfma_s_first(rg.s[HALF], rg.fr[0], qf[0]);
-            else if ((f & 1) == 0) f4_mfma_s(rg.s[HALF], rg.fr[f & 7], qf[f >> 1]);
-            else if (f == 1) q4_mfma_c_first(rg.dp[HALF], rg.fr[1], dof[0], rg.ndl);
-            else f4_mfma_s(rg.dp[HALF], rg.fr[f & 7], dof[f >> 1]);
+            constexpr int f = (M >> 1) ^ 1, qh = M & 1;      // even = K (S^T), odd = V (dP'^T)
+            constexpr int s = f >> 2, t = 2 * qh + ((f >> 1) & 1);
+            if constexpr ((f & 1) == 0) {
+                if constexpr (s == 0) q4_mfma_first(rg.s[HALF][t], rg.fr[f & 7], qf[4 * qh]);
+                else q4_mfma(rg.s[HALF][t], rg.fr[f & 7], qf[4 * qh + s]);
+            } else {
+                if constexpr (s == 0) q4_mfma_c_first(rg.dp[HALF][t], rg.fr[f & 7], dof[4 * qh], rg.ndl[qh]);
+                else q4_mfma(rg.dp[HALF][t], rg.fr[f & 7], dof[4 * qh + s]);
+            }
         }
-        if (DMA && (m & 1)) {
-            const int j = m >> 2;
-            if ((m & 2) == 0) f4_dma1(vk[j], dm.q_src, dm.dst + 4096 * j);
+        if constexpr (DMA && (M & 3) == 3) {
+            constexpr int i = M >> 2, j = i >> 1;
+            if constexpr ((i & 1) == 0) f4_dma1(vk[j], dm.q_src, dm.dst + 4096 * j);
             else f4_dma1(vv[j], dm.do_src, dm.dst + kD4TileBytes + 4096 * j);
         }
-        if (HAS_PREV) q4_fill_at<8, 16, HALF ^ 1>(8 + m, cx, rg);
+        if constexpr (HAS_PREV) q4_fillers<16 + M, HALF ^ 1>(cx, rg);
         sched_fence();
+        q4_x<HALF, HAS_PREV, DMA, M + 1>(cx, rg, qf, dof, vk, vv, dm);
     }
 }
 
-// masks of a unit on its transposed scores (lwm/llama.py:572-592): key row (r&3) + 8 (r>>2) + 4 hi of the unit is visible to
-// this lane's query iff it is not after it (rel = query position - position of the unit's key 0 - 4 hi, clamped) and, with
-// key meta, carries the query's segment (kSegInvalid: a padded / out-of-range key)
+// masks of a unit on its transposed scores (lwm/llama.py:572-592): key row 16 kh + 4g + j of the unit is visible to the
+// lane's query of half qh iff it is not after it (rel[qh] = query position - position of the unit's key 0 - 4g, clamped)
+// and, with key meta, carries the query's segment (kSegInvalid: a padded / out-of-range key)
 template <int HALF, bool HAS_META>
-LWM_DEVICE void q4_mask(const Q4Ctx& cx, f32x16& s, int rel, int32_t seg_q) {
+LWM_DEVICE void q4_mask(const Q4Ctx& cx, f32x4 (&s)[4], const int (&rel)[2], const int32_t (&seg_q)[2]) {
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        if (HAS_META) {
-            const u32x4 sg = lds_read_u32x4(cx.meta + HALF * 32 * 4 + 8 * g * 4);
+    for (int kh = 0; kh < 2; ++kh) {
+        u32x4 sg = {0u, 0u, 0u, 0u};
+        if (HAS_META) sg = lds_read_u32x4(cx.meta + HALF * 32 * 4 + 16 * kh * 4);
+#pragma unroll
+        for (int qh = 0; qh < 2; ++qh)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const bool vis = ((int32_t)sg[j] == seg_q) && (8 * g + j <= rel);
-                s[4 * g + j] = vis ? s[4 * g + j] : -INFINITY;
+                const bool vis = (!HAS_META || (int32_t)sg[j] == seg_q[qh]) && (16 * kh + j <= rel[qh]);
+                s[2 * qh + kh][j] = vis ? s[2 * qh + kh][j] : -INFINITY;
             }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) s[4 * g + j] = (8 * g + j <= rel) ? s[4 * g + j] : -INFINITY;
-        }
     }
 }
 
-// Phase Y of unit u: dQ^T += K(u-1)^T dS^T(u-1)  ||  gaps 0..7 of unit u.  INIT: the first products of the walk.
-template <int HALF, bool HAS_PREV, bool INIT>
-LWM_DEVICE void q4_y(const Q4Ctx& cx, Q4Regs& rg, f32x16 (&dq)[4]) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int m = 16 + j;
-        if ((j & 1) == 0) {
-            rg.fr[(m + kD4Ahead) & 7] = q4_frag<HALF>(cx, m + kD4Ahead);
-            rg.fr[(m + kD4Ahead + 1) & 7] = q4_frag<HALF>(cx, m + kD4Ahead + 1);
+// Phase Y of unit u: dQ^T += K(u-1)^T dS^T(u-1), 16 MFMAs (d block j>>1, query half j&1)  ||  gaps 0..15 of unit u.
+// INIT: the first products of the walk.
+template <int HALF, bool HAS_PREV, bool INIT, int J = 0>
+LWM_DEVICE void q4_y(const Q4Ctx& cx, Q4Regs& rg, f32x4 (&dq)[16]) {
+    if constexpr (J < 16) {
+        if constexpr ((J & 3) == 0) {
+            constexpr int f0 = 16 + (J >> 1) + kD4Ahead;
+            rg.fr[f0 & 7] = q4_frag<HALF>(cx, f0);
+            sched_fence();      // (the pair in this order: the wait for the younger fragment then covers both)
+            rg.fr[(f0 + 1) & 7] = q4_frag<HALF>(cx, f0 + 1);
         }
         sched_fence();
-        if (HAS_PREV) {
-            const int jf = j ^ 1;      // (pairs: the younger fragment first -- one wait per two MFMAs)
-            if (INIT && jf < 4) d4_mfma_o_first(dq[jf & 3], rg.fr[(16 + jf) & 7], rg.dsb[0]);
-            else f4_mfma_o(dq[jf & 3], rg.fr[(16 + jf) & 7], rg.dsb[jf >> 2]);
+        if constexpr (HAS_PREV) {
+            constexpr int db = (J >> 1) ^ 1, qh = J & 1;      // (pairs: the younger fragment first)
+            if constexpr (INIT) q4_mfma_o_first(dq[2 * db + qh], rg.fr[(16 + db) & 7], rg.dsb[qh]);
+            else q4_mfma_o(dq[2 * db + qh], rg.fr[(16 + db) & 7], rg.dsb[qh]);
         }
-        q4_fill_at<0, 8, HALF>(j, cx, rg);
+        q4_fillers<J, HALF>(cx, rg);
         sched_fence();
+        q4_y<HALF, HAS_PREV, INIT, J + 1>(cx, rg, dq);
     }
 }
 
+template <int PAR, int G = 16>
+LWM_DEVICE void q4_drain_fill(const Q4Ctx& cx, Q4Regs& rg) {
+    if constexpr (G < 48) {
+        q4_fillers<G, PAR>(cx, rg);
+        q4_drain_fill<PAR, G + 1>(cx, rg);
+    }
+}
+template <int J = 0>
+LWM_DEVICE void q4_drain_mfma(Q4Regs& rg, f32x4 (&dq)[16]) {
+    if constexpr (J < 16) {
+        q4_mfma_o(dq[J], rg.fr[J >> 1], rg.dsb[J & 1]);
+        q4_drain_mfma<J + 1>(rg, dq);
+    }
+}
 template <int PAR>
-LWM_DEVICE void q4_drain(const Q4Ctx& cx, Q4Regs& rg, f32x16 (&dq)[4]) {
-#pragma unroll
-    for (int g = 8; g < 24; ++g) q4_fill_at<8, 16, PAR>(g, cx, rg);
+LWM_DEVICE void q4_drain(const Q4Ctx& cx, Q4Regs& rg, f32x4 (&dq)[16]) {
+    q4_drain_fill<PAR>(cx, rg);
 #pragma unroll
     for (int j = 0; j < 8; ++j) rg.fr[j] = q4_frag<0>(cx, 16 + j);
     sched_fence();
-#pragma unroll
-    for (int j = 0; j < 8; ++j) f4_mfma_o(dq[j & 3], rg.fr[j], rg.dsb[j >> 2]);
+    q4_drain_mfma(rg, dq);
 }
 
 // per-lane byte offsets of the wave's four pieces of a 64-row K / V tile, rows clamped to Sk-1 (rows past Sk are masked
-// through the key meta)
+// through the key meta); lane l writes physical slot l&15 of its row, so it fetches logical slot (l&15) ^ q4_swz(row)
 LWM_DEVICE void q4_stage_offsets(const AttnParams& p, int wave, int lane, int st, uint32_t (&vk)[4], uint32_t (&vv)[4]) {
     const int slot = lane & 15;
     for (int j = 0; j < 4; ++j) {
@@ -955,9 +1045,39 @@ LWM_DEVICE void q4_stage_offsets(const AttnParams& p, int wave, int lane, int st
         int krow = st * kQ4BK + row;
         krow = krow < p.Sk ? krow : p.Sk - 1;
         const int rel = krow - st * kQ4BK;
-        const int col = (slot ^ swz(row)) << 3;
+        const int col = (slot ^ q4_swz(row)) << 3;
         vk[j] = (uint32_t)(((int64_t)rel * p.k_ss + col) * 2);
         vv[j] = (uint32_t)(((int64_t)rel * p.v_ss + col) * 2);
+    }
+}
+
+// the stores of query half QH: row q_row of (b, h), 4 consecutive d per d block (what the stores share is read once and
+// the three cases are three loops: left inside one loop, hipcc re-read carry_in / final_out behind a wait per store --
+// see d4_store_tiles)
+template <int QH>
+LWM_DEVICE void q4_store(const AttnParams& p, const f32x4 (&dq)[16], int b, int h, int q_row, int g4) {
+    const bool carry = p.carry_in != 0, fin = p.final_out != 0;
+    const float sc = p.scale;
+    bf16_t* const op = p.dq + (int64_t)b * p.dq_sb + (int64_t)q_row * p.dq_ss + (int64_t)h * p.dq_sh + 4 * g4;
+    float* const ap = p.dq_acc + (int64_t)b * p.dqa_sb + (int64_t)q_row * p.dqa_ss + (int64_t)h * p.dqa_sh + 4 * g4;
+    if (fin && !carry) {
+#pragma unroll
+        for (int db = 0; db < 8; ++db) {
+            const f32x4 a = dq[2 * db + QH];
+            global_store_b64(op + 16 * db, u32x2{pack_bf16x2(a[0] * sc, a[1] * sc), pack_bf16x2(a[2] * sc, a[3] * sc)});
+        }
+    } else {
+#pragma unroll
+        for (int db = 0; db < 8; ++db) {
+            const f32x4 a = dq[2 * db + QH];
+            float o0 = a[0] * sc, o1 = a[1] * sc, o2 = a[2] * sc, o3 = a[3] * sc;
+            if (carry) {
+                const f32x4 c = global_load_f32x4(ap + 16 * db);
+                o0 += c[0]; o1 += c[1]; o2 += c[2]; o3 += c[3];
+            }
+            if (fin) global_store_b64(op + 16 * db, u32x2{pack_bf16x2(o0, o1), pack_bf16x2(o2, o3)});
+            else global_store_f32x4(ap + 16 * db, f32x4{o0, o1, o2, o3});
+        }
     }
 }
 
@@ -965,7 +1085,7 @@ template <bool HAS_META>
 LWM_DEVICE void attn_bwd_dq4_body(const AttnParams& p) {
     const lds_t lds = dyn_lds();
     const int tid = thread_idx();
-    const int wave = wave_uniform(tid >> 6), lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
+    const int wave = wave_uniform(tid >> 6), lane = tid & 63, l15 = lane & 15, g4 = lane >> 4;
 
     // ---- block -> (q block, head, batch): all q blocks of one (b,h) on one XCD, longest walks (the last blocks) first
     const int nqb = (p.Sq + kQ4BQ - 1) / kQ4BQ;
@@ -985,25 +1105,38 @@ LWM_DEVICE void attn_bwd_dq4_body(const AttnParams& p) {
     const bf16_t* vb = p.v + (int64_t)b * p.v_sb + (int64_t)h * p.v_sh;
     const bf16_t* dob = p.dout + (int64_t)b * p.do_sb + (int64_t)h * p.do_sh;
 
-    // ---- this lane's query: fragments straight into the accumulator file (a row past Sq re-reads the last row: its
-    // results are never stored), its statistics
-    const int q_row = qbi * kQ4BQ + wave * 32 + l31;
-    const bool q_ok = q_row < p.Sq;
-    const int qr = q_ok ? q_row : p.Sq - 1;
-    bf16x8 qf[8], dof[8];
-    for (int s = 0; s < 8; ++s) qf[s] = f4_load_agpr(qb + (int64_t)qr * p.q_ss + 16 * s + 8 * hi);
-    for (int s = 0; s < 8; ++s) dof[s] = f4_load_agpr(dob + (int64_t)qr * p.do_ss + 16 * s + 8 * hi);
+    // ---- this lane's two queries (row 16 qh + c of the wave's 32): fragments straight into the accumulator file (a row
+    // past Sq re-reads the last row: its results are never stored), their statistics
+    int q_row[2], qr[2];
+    bool q_ok[2];
+#pragma unroll
+    for (int qh = 0; qh < 2; ++qh) {
+        q_row[qh] = qbi * kQ4BQ + wave * 32 + 16 * qh + l15;
+        q_ok[qh] = q_row[qh] < p.Sq;
+        qr[qh] = q_ok[qh] ? q_row[qh] : p.Sq - 1;
+    }
+    bf16x8 qf[8], dof[8];       // [4 qh + s]: d step s of 32
+#pragma unroll
+    for (int i = 0; i < 8; ++i) qf[i] = f4_load_agpr(qb + (int64_t)qr[i >> 2] * p.q_ss + 32 * (i & 3) + 8 * g4);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) dof[i] = f4_load_agpr(dob + (int64_t)qr[i >> 2] * p.do_ss + 32 * (i & 3) + 8 * g4);
     Q4Ctx cx;
     Q4Regs rg;
     {
         const int64_t Sqp = bwd_stat_pad(p.Sq), srow = bwd_stat_row((int64_t)b * p.H + h, Sqp);
-        cx.nl = q_ok ? p.delta[srow + qr] : -INFINITY;
-        const float nd = p.delta[srow + Sqp + qr];
-        for (int r = 0; r < 16; ++r) rg.ndl[r] = nd;
+#pragma unroll
+        for (int qh = 0; qh < 2; ++qh) {
+            cx.nl[qh] = q_ok[qh] ? p.delta[srow + qr[qh]] : -INFINITY;
+            const float nd = p.delta[srow + Sqp + qr[qh]];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) rg.ndl[qh][r] = nd;
+        }
         q4_opaque(rg.ndl);
     }
     cx.c = p.scale * kLog2e;
-    const int32_t seg_q = (HAS_META && q_ok && p.seg_q) ? p.seg_q[(int64_t)b * p.Sq + q_row] : 0;
+    int32_t seg_q[2];
+#pragma unroll
+    for (int qh = 0; qh < 2; ++qh) seg_q[qh] = (HAS_META && q_ok[qh] && p.seg_q) ? p.seg_q[(int64_t)b * p.Sq + q_row[qh]] : 0;
     const PosMap km = k_map(p);
     const PosTab kt_ = load_postab(km);                           // (register copies of the tables: prologue only)
     const int64_t q_base = pos_base(load_postab(q_map(p)), qbi * kQ4BQ);       // position of query row r of this workgroup = q_base + r
@@ -1023,26 +1156,25 @@ LWM_DEVICE void attn_bwd_dq4_body(const AttnParams& p) {
     }
     const int n = nst > st0 ? nst - st0 : 0;       // walk index i -> key step st0 + i (ascending)
 
-    f32x16 dq[4];
+    f32x4 dq[16];               // [2 db + qh]: dQ^T rows 16 db + 4g + 0..3 of query 16 qh + c
     if (n == 0)
-        for (int i = 0; i < 4; ++i) dq[i] = zero_f32x16();
+#pragma unroll
+        for (int i = 0; i < 16; ++i) dq[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     if (n == 0) {
         f4_load_agpr_wait8(qf);
         f4_load_agpr_wait8(dof);
     }
 
     if (n > 0) {
-        for (int s = 0; s < 8; ++s) cx.ka[s] = lds + tile_off(l31, 2 * s + hi);
-        {
-            const TrFragAddr t = frag_tr_addr(lds, lane);
-            for (int db = 0; db < 4; ++db) {
-                cx.tlo[db] = t.lo[db];
-                cx.tup[db] = t.up[db];
-                cx.plo[db] = t.lo[db];
-                cx.pup[db] = t.up[db];
-            }
+#pragma unroll
+        for (int s = 0; s < 4; ++s) cx.ka[s] = lds + q4_tile_off(l15, 4 * s + g4);
+#pragma unroll
+        for (int db = 0; db < 8; ++db) {
+            // lane t of a 16-lane group addresses key 4g + (t>>2), d 16 db + 4 (t&3): four keys x 16 d per group
+            cx.tlo[db] = lds + q4_tile_off(4 * g4 + (l15 >> 2), 2 * db + ((l15 & 3) >> 1)) + (l15 & 1) * 8;
+            cx.plo[db] = cx.tlo[db];
         }
-        cx.meta = lds + kQ4OffMeta + 16 * hi;
+        cx.meta = lds + kQ4OffMeta + 16 * g4;
         const int64_t k_step_bytes = (int64_t)kQ4BK * p.k_ss * 2, v_step_bytes = (int64_t)kQ4BK * p.v_ss * 2;
         uint32_t vk[4], vv[4];
         q4_stage_offsets(p, wave, lane, 0, vk, vv);       // full steps: nothing is clamped
@@ -1085,7 +1217,9 @@ LWM_DEVICE void attn_bwd_dq4_body(const AttnParams& p) {
 
         auto clamp32 = [](int64_t x) -> int { return x > (1 << 30) ? (1 << 30) : (x < -(1 << 30) ? -(1 << 30) : (int)x); };
         // positions relative to k_start; a unit's first key (row ub of the K/V block) sits at rel_pos(km, ub)
-        const int q_rel = clamp32(q_base + q_row - p.k_start) - 4 * hi;                         // this lane's query
+        int q_rel[2];                                                                    // this lane's queries
+#pragma unroll
+        for (int qh = 0; qh < 2; ++qh) q_rel[qh] = clamp32(q_base + q_row[qh] - p.k_start) - 4 * g4;
         PosCursor kc = cursor_begin(kt_);
         auto k_rel_of = [&](int ub) -> int {             // (the walk ascends)
             cursor_seek(km, kc, ub);
@@ -1097,34 +1231,50 @@ LWM_DEVICE void attn_bwd_dq4_body(const AttnParams& p) {
         auto needs_causal = [&](int ub) -> bool { return ub >= mask_from; };
         // the wave's 32 queries of one segment?  (then a step whose 64 keys carry it needs no segment test; rows past Sq
         // are never stored and do not count)
-        const int32_t own_seg = wave_uniform(seg_q);
-        const bool own_uniform = HAS_META && !wave_any(q_ok && seg_q != own_seg);
-        auto rel_of = [&](int ub) -> int {
-            if (!p.causal) return 64;
-            const int64_t d = (int64_t)q_rel - k_rel_of(ub);
-            return d > 64 ? 64 : (d < -64 ? -64 : (int)d);
+        const int32_t own_seg = wave_uniform(seg_q[0]);
+        const bool own_uniform = HAS_META && !wave_any((q_ok[0] && seg_q[0] != own_seg) || (q_ok[1] && seg_q[1] != own_seg));
+        auto rel_of = [&](int ub, int (&rel)[2]) {
+            if (!p.causal) {
+                rel[0] = rel[1] = 64;
+                return;
+            }
+            const int kr = k_rel_of(ub);
+#pragma unroll
+            for (int qh = 0; qh < 2; ++qh) {
+                const int64_t d = (int64_t)q_rel[qh] - kr;
+                rel[qh] = d > 64 ? 64 : (d < -64 ? -64 : (int)d);
+            }
         };
 
-        for (int par = 0; par < 2; ++par) {
-            rg.s[par] = zero_f32x16();
-            rg.dp[par] = zero_f32x16();
-        }
+#pragma unroll
+        for (int par = 0; par < 2; ++par)
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                rg.s[par][t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+                rg.dp[par][t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            }
+#pragma unroll
         for (int r = 0; r < 16; ++r) {
             rg.t[r] = 0.0f;
             rg.ds[r] = 0.0f;
         }
+#pragma unroll
         for (int t = 0; t < 2; ++t) rg.dsb[t] = zero_bf16x8();
+#pragma unroll
         for (int j = 0; j < 8; ++j) rg.fr[j] = zero_bf16x8();
         D4Dma dm = {};
+#pragma unroll
         for (int j = 0; j < kD4Ahead; ++j) rg.fr[j] = q4_frag<0>(cx, j);
 
 #define LWM_Q4_MASK(HALF_, HAS_PREV_, ub_)                                                                          \
     do {                                                                                                            \
-        if (!(HAS_PREV_)) d4_settle_t(rg.s[HALF_]);     /* no MFMA stands between the S chain and its first reader */ \
+        if (!(HAS_PREV_)) q4_settle_t(rg.s[HALF_]);     /* no MFMA stands between the S chains and their first reader */ \
         if ((HAS_META && !uni_) || needs_causal(ub_)) {                                                             \
-            if (HAS_PREV_) d4_settle_t(rg.s[HALF_]);                                                                \
-            if (HAS_META && !uni_) q4_mask<HALF_, HAS_META>(cx, rg.s[HALF_], rel_of(ub_), seg_q);                   \
-            else q4_mask<HALF_, false>(cx, rg.s[HALF_], rel_of(ub_), seg_q);                                        \
+            if (HAS_PREV_) q4_settle_t(rg.s[HALF_]);                                                                \
+            int rel_[2];                                                                                            \
+            rel_of(ub_, rel_);                                                                                      \
+            if (HAS_META && !uni_) q4_mask<HALF_, HAS_META>(cx, rg.s[HALF_], rel_, seg_q);                          \
+            else q4_mask<HALF_, false>(cx, rg.s[HALF_], rel_, seg_q);                                               \
         }                                                                                                           \
     } while (0)
         int ub = st0 * kQ4BK;
@@ -1142,24 +1292,22 @@ LWM_DEVICE void attn_bwd_dq4_body(const AttnParams& p) {
         }                                                                                                           \
         const uint32_t d_ = (((i) & 3) == 3) ? (uint32_t)(-3 * kD4SlotBytes) : (uint32_t)kD4SlotBytes;             \
         const uint32_t e_ = (((i) & 3) == 3) ? (uint32_t)(-3 * kQ4BK * 4) : (uint32_t)(kQ4BK * 4);                 \
-        const int32_t segw_ = HAS_META ? seg_step_word(cx.meta - 16 * hi, lane) : 0;                               \
+        const int32_t segw_ = HAS_META ? seg_step_word(cx.meta - 16 * g4, lane) : 0;                               \
         q4_x<0, !(FIRST), PIPE>(cx, rg, qf, dof, vk, vv, dm);                                                       \
         const bool uni_ = HAS_META && seg_step_uniform(segw_, own_uniform, own_seg);                                \
         LWM_Q4_MASK(0, !(FIRST), ub);                                                                               \
         q4_y<0, !(FIRST), false>(cx, rg, dq);                                                                       \
         q4_x<1, true, false>(cx, rg, qf, dof, vk, vv, dm);                                                          \
-        for (int s_ = 0; s_ < 8; ++s_) cx.ka[s_] += d_;                                                             \
+        for (int s_ = 0; s_ < 4; ++s_) cx.ka[s_] += d_;                                                             \
         LWM_Q4_MASK(1, true, ub + 32);                                                                              \
         q4_y<1, true, FIRST>(cx, rg, dq);                                                                           \
         ub += kQ4BK;                                                                                                \
-        if ((FIRST) || !(PIPE)) d4_settle_acc4(dq);                                                                 \
+        if ((FIRST) || !(PIPE)) q4_settle_acc(dq);                                                                  \
         glds_wait_all();                                                                                            \
         block_sync_lds();                                                                                           \
-        for (int db_ = 0; db_ < 4; ++db_) {                                                                         \
+        for (int db_ = 0; db_ < 8; ++db_) {                                                                         \
             cx.plo[db_] = cx.tlo[db_];                                                                              \
-            cx.pup[db_] = cx.tup[db_];                                                                              \
             cx.tlo[db_] += d_;                                                                                      \
-            cx.tup[db_] += d_;                                                                                      \
         }                                                                                                           \
         cx.meta += e_;                                                                                              \
     } while (0)
@@ -1188,42 +1336,13 @@ LWM_DEVICE void attn_bwd_dq4_body(const AttnParams& p) {
 #undef LWM_Q4_MASK
         // the last unit's product: its K tile is the second half of the PREVIOUS slot now (the registers moved on)
         q4_drain<1>(cx, rg, dq);
-        d4_settle_acc4(dq);      // before the paths merge
+        q4_settle_acc(dq);      // before the paths merge
     }
 
-    // ---- epilogue: scale, merge with the ring carry, store (one query row per lane)
-    d4_settle_acc4(dq);
-    // (what the 16 stores share is read once and the three cases are three loops: left inside one loop, hipcc re-read
-    // carry_in / final_out behind a wait per store -- see d4_store_tiles)
-    if (q_ok) {
-        const bool carry = p.carry_in != 0, fin = p.final_out != 0;
-        const float sc = p.scale;
-        bf16_t* const op = p.dq + (int64_t)b * p.dq_sb + (int64_t)q_row * p.dq_ss + (int64_t)h * p.dq_sh + 4 * hi;
-        float* const ap = p.dq_acc + (int64_t)b * p.dqa_sb + (int64_t)q_row * p.dqa_ss + (int64_t)h * p.dqa_sh + 4 * hi;
-        if (fin && !carry) {
-#pragma unroll
-            for (int db = 0; db < 4; ++db)
-#pragma unroll
-                for (int rq = 0; rq < 4; ++rq)
-                    global_store_b64(op + 32 * db + 8 * rq, u32x2{pack_bf16x2(dq[db][4 * rq + 0] * sc, dq[db][4 * rq + 1] * sc),
-                                                                  pack_bf16x2(dq[db][4 * rq + 2] * sc, dq[db][4 * rq + 3] * sc)});
-        } else {
-#pragma unroll
-            for (int db = 0; db < 4; ++db)
-#pragma unroll
-                for (int rq = 0; rq < 4; ++rq) {
-                    const int d0 = 32 * db + 8 * rq;
-                    float o0 = dq[db][4 * rq + 0] * sc, o1 = dq[db][4 * rq + 1] * sc;
-                    float o2 = dq[db][4 * rq + 2] * sc, o3 = dq[db][4 * rq + 3] * sc;
-                    if (carry) {
-                        const f32x4 a = global_load_f32x4(ap + d0);
-                        o0 += a[0]; o1 += a[1]; o2 += a[2]; o3 += a[3];
-                    }
-                    if (fin) global_store_b64(op + d0, u32x2{pack_bf16x2(o0, o1), pack_bf16x2(o2, o3)});
-                    else global_store_f32x4(ap + d0, f32x4{o0, o1, o2, o3});
-                }
-        }
-    }
+    // ---- epilogue: scale, merge with the ring carry, store (a query row per lane and half: 16 stores of 4 consecutive d)
+    q4_settle_acc(dq);
+    if (q_ok[0]) q4_store<0>(p, dq, b, h, q_row[0], g4);
+    if (q_ok[1]) q4_store<1>(p, dq, b, h, q_row[1], g4);
 }
 
 LWM_KERNEL(kD4Threads) void attn_bwd_dq4_kernel(AttnParams p) { attn_bwd_dq4_body<false>(p); }

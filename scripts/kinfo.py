@@ -6,7 +6,7 @@ import re
 import sys
 from collections import Counter
 
-KEYS = ['v_mfma_f32_32x32x16_bf16', 'v_accvgpr_read_b32', 'v_accvgpr_write_b32', 'v_mov_b32_e32', 'scratch_load_dword',
+KEYS = ['v_mfma_f32_32x32x16_bf16', 'v_mfma_f32_16x16x32_bf16', 'v_accvgpr_read_b32', 'v_accvgpr_write_b32', 'v_mov_b32_e32', 'scratch_load_dword',
         'scratch_store_dword', 's_waitcnt', 's_nop', 'ds_read_b128', 'ds_read_b64_tr_b16', 'v_exp_f32_e32', 'v_fma_f32',
         'v_mul_f32_e32', 'v_cvt_pk_bf16_f32', 'global_load_lds_dwordx4', 's_barrier', 'v_add_u32_e32', 'v_xor_b32_e32',
         'v_cndmask_b32_e32', 'v_readfirstlane_b32']
@@ -106,9 +106,10 @@ def main():
         blocks.append((curname, cur))
         for nm, b in blocks:
             cc = Counter(x.split()[0] for x in b)
-            if cc.get('v_mfma_f32_32x32x16_bf16', 0):
+            n_mfma = cc['v_mfma_f32_32x32x16_bf16'] + cc['v_mfma_f32_16x16x32_bf16']      # (a kernel uses one shape)
+            if n_mfma:
                 print('%-12s n=%4d mfma=%3d accrd=%3d accwr=%3d mov=%3d wait=%3d nop=%3d dsr=%3d tr=%3d dma=%2d valu(fma/exp/mul/cvt)=%d/%d/%d/%d add=%d' % (
-                    nm, len(b), cc['v_mfma_f32_32x32x16_bf16'], cc['v_accvgpr_read_b32'], cc['v_accvgpr_write_b32'],
+                    nm, len(b), n_mfma, cc['v_accvgpr_read_b32'], cc['v_accvgpr_write_b32'],
                     cc['v_mov_b32_e32'], cc['s_waitcnt'], cc['s_nop'], cc['ds_read_b128'], cc['ds_read_b64_tr_b16'],
                     cc['global_load_lds_dwordx4'], cc['v_fma_f32'], cc['v_exp_f32'], cc['v_mul_f32'], cc['v_cvt_pk_bf16_f32'],
                     cc['v_add_u32_e32']))

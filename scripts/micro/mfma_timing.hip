@@ -49,6 +49,26 @@ __global__ __launch_bounds__(512) void mfma_time(unsigned long long* out, float*
     if (s == 12345.f) sink[0] = s;
 }
 
+// Operand maps of v_mfma_f32_16x16x32_bf16 (the dQ kernel's shape), lane l: A holds row l&15, k = 8(l>>4)+j; B column
+// l&15, the same k; D column l&15, rows 4(l>>4)+j.  With A[r][k] = (r+1)[k == r] and B[k][c] = (c+1)[k < 16] built from
+// those maps, D[r][c] = (r+1)(c+1): the kernel stores every lane's four registers, mfma_timing.py compares.
+__global__ __launch_bounds__(64) void mfma16_layout(float* out) {
+    const int l = thread_idx() & 63, c = l & 15, g = l >> 4;
+    bf16x8 a, b;
+    for (int j = 0; j < 8; ++j) {
+        const int k = 8 * g + j;
+        a[j] = (bf16_t)(k == c ? (float)(c + 1) : 0.0f);
+        b[j] = (bf16_t)(k < 16 ? (float)(c + 1) : 0.0f);
+    }
+    f32x4 d = {0.0f, 0.0f, 0.0f, 0.0f};
+    d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, d, 0, 0, 0);
+    for (int j = 0; j < 4; ++j) out[4 * l + j] = d[j];
+}
+extern "C" int mfma16_layout_run(void* out, void* stream) {
+    hipLaunchKernelGGL(mfma16_layout, dim3(1), dim3(64), 0, (hipStream_t)stream, (float*)out);
+    return (int)hipGetLastError();
+}
+
 template <int NACC, int MODE, int NVALU>
 static void run1(unsigned long long* out, float* sink, int threads, int iters, hipStream_t st) {
     hipLaunchKernelGGL((mfma_time<NACC, MODE, NVALU>), dim3(1), dim3(threads), 64 * 256, st, out, sink, iters);
