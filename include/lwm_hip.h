@@ -393,6 +393,36 @@ typedef struct LwmKv8DecodeArgs {
 } LwmKv8DecodeArgs;
 int lwm_attn_decode_kv8(const LwmKv8DecodeArgs* args, void* stream);
 
+/* A BLOCK of Sq queries over that cache (lwm_version() >= 530): chunked prefill, a block appended to a live cache.
+ * Key j < Sk is visible to query i iff j <= q_start + i and key_valid[b, j] != 0 (key_valid NULL: all valid) -- the
+ * structured mask of lwm_attn_fwd with causal = 1, k_start = 0.  The kernel is lwm_attn_fwd's split-K kernel with the
+ * staging replaced: e4m3 bytes and scales are dequantised on their way into LDS (exactly: q * s is a bf16 number), no
+ * bf16 copy of the cache exists in memory, and the partials are bit for bit those of lwm_attn_fwd (final_out = 0, the
+ * same k_splits >= 2) over a bf16 copy.  Output: normalised partials out_acc [k_splits,B,Sq,H,D] f32 and lse_acc
+ * [k_splits,B,H,Sq] f32 (k_splits 0 and 1: one piece), merged by lwm_attn_combine; a row that sees nothing gives
+ * (0, -inf); masked rows and rows at or past Sk contribute nothing whatever their bytes and scales hold.  D = 128,
+ * Sq >= 1, Sk >= 1, 0 <= k_splits <= 4096; alignment and strides as lwm_attn_decode_kv8; key_valid_stride_b in bytes. */
+typedef struct LwmKv8PrefillArgs {
+    LwmTensor4 q;                   /* bf16 (B,Sq,H,D) */
+    const void* k;                  /* e4m3 bytes (B,Sk,H,D) */
+    const void* v;
+    int64_t k_stride_b, k_stride_s, k_stride_h;
+    int64_t v_stride_b, v_stride_s, v_stride_h;
+    const float* k_scale;           /* (B,Sk,H) */
+    const float* v_scale;
+    int64_t k_scale_stride_b, k_scale_stride_s;
+    int64_t v_scale_stride_b, v_scale_stride_s;
+    const uint8_t* key_valid;       /* (B,Sk) u8, nonzero = valid; NULL = all valid */
+    int64_t key_valid_stride_b;
+    int32_t B, Sq, Sk, H, D;
+    int64_t q_start;                /* position of query row 0 (= the cache index the block was written at) */
+    float scale;                    /* softmax scale, > 0 */
+    int32_t k_splits;
+    float* out_acc;
+    float* lse_acc;
+} LwmKv8PrefillArgs;
+int lwm_attn_prefill_kv8(const LwmKv8PrefillArgs* args, void* stream);
+
 /* Elementwise helpers of the ring driver (HBM-bound). */
 /* dst_bf16[n] = (bf16) src_f32[n] */
 int lwm_cast_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream);
@@ -589,7 +619,7 @@ int lwm_vq_gather_f32(const float* codebook, const int32_t* idx, const float* z,
 const char* lwm_last_error(void);
 int lwm_version(void);
 /* sizeof(LwmAttnArgs) (which = 0) / sizeof(LwmConvArgs) (1) / sizeof(LwmRingArgs) (2) / sizeof(LwmGemvArgs) (3) /
- * sizeof(LwmSampleArgs) (4) / sizeof(LwmKv8DecodeArgs) (5) as compiled into the library:
+ * sizeof(LwmSampleArgs) (4) / sizeof(LwmKv8DecodeArgs) (5) / sizeof(LwmKv8PrefillArgs) (6) as compiled into the library:
  * lets a foreign-language binding verify its struct mirror at load time. */
 int lwm_sizeof(int which);
 

@@ -100,6 +100,21 @@ class LwmKv8DecodeArgs(C.Structure):
     ]
 
 
+class LwmKv8PrefillArgs(C.Structure):
+    _fields_ = [
+        ("q", LwmTensor4), ("k", C.c_void_p), ("v", C.c_void_p),
+        ("k_stride_b", C.c_int64), ("k_stride_s", C.c_int64), ("k_stride_h", C.c_int64),
+        ("v_stride_b", C.c_int64), ("v_stride_s", C.c_int64), ("v_stride_h", C.c_int64),
+        ("k_scale", C.c_void_p), ("v_scale", C.c_void_p),
+        ("k_scale_stride_b", C.c_int64), ("k_scale_stride_s", C.c_int64),
+        ("v_scale_stride_b", C.c_int64), ("v_scale_stride_s", C.c_int64),
+        ("key_valid", C.c_void_p), ("key_valid_stride_b", C.c_int64),
+        ("B", C.c_int32), ("Sq", C.c_int32), ("Sk", C.c_int32), ("H", C.c_int32), ("D", C.c_int32),
+        ("q_start", C.c_int64), ("scale", C.c_float), ("k_splits", C.c_int32),
+        ("out_acc", C.c_void_p), ("lse_acc", C.c_void_p),
+    ]
+
+
 class LwmSampleArgs(C.Structure):
     _fields_ = [
         ("logits", C.c_void_p), ("ld", C.c_int64), ("rows", C.c_int32), ("V", C.c_int32),
@@ -180,6 +195,7 @@ PROTOTYPES = {
                                          C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
                                          C.c_void_p]),
     "lwm_attn_decode_kv8": (C.c_int, [C.POINTER(LwmKv8DecodeArgs), C.c_void_p]),
+    "lwm_attn_prefill_kv8": (C.c_int, [C.POINTER(LwmKv8PrefillArgs), C.c_void_p]),
     "lwm_rope_bf16": (C.c_int, [LwmTensor4, LwmTensor4, C.c_void_p, C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p]),
     "lwm_rmsnorm_fwd_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
                                       C.c_float, C.c_void_p]),
@@ -225,7 +241,8 @@ def bind(lib):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
-    for which, cls in ((0, LwmAttnArgs), (1, LwmConvArgs), (2, LwmRingArgs), (4, LwmSampleArgs), (5, LwmKv8DecodeArgs)):
+    for which, cls in ((0, LwmAttnArgs), (1, LwmConvArgs), (2, LwmRingArgs), (4, LwmSampleArgs), (5, LwmKv8DecodeArgs),
+                       (6, LwmKv8PrefillArgs)):
         if lib.lwm_sizeof(which) != C.sizeof(cls):
             raise ImportError(f"{cls.__name__}: ctypes mirror is {C.sizeof(cls)} bytes, library has "
                               f"{lib.lwm_sizeof(which)} (include/lwm_hip.h and lwm_amd/_capi.py out of step)")

@@ -5,6 +5,7 @@
 // misc_kernels.h and "lwm_hip.h" already included.
 #include "sample.h"
 #include "attn_decode_kv8.h"
+#include "attn_prefill_kv8.h"
 
 namespace lwm {
 
@@ -283,6 +284,43 @@ int lwm_attn_decode_kv8(const LwmKv8DecodeArgs* a, void* stream) {
     p.B = a->B; p.Sk = a->Sk; p.H = a->H; p.k_splits = a->k_splits > 1 ? a->k_splits : 1;
     p.scale = a->scale; p.out_acc = a->out_acc; p.lse_acc = a->lse_acc;
     return launch("attn_decode_kv8", attn_decode_kv8_kernel, (long)p.B * p.k_splits, kDecThreads, kDec8LdsBytes, stream, p);
+}
+
+int lwm_attn_prefill_kv8(const LwmKv8PrefillArgs* a, void* stream) {
+    using namespace lwm;
+    if (!a) return fail(LWM_EINVAL, "%s", "attn_prefill_kv8: args is null");
+    int r;
+    if ((r = check_t4("q", a->q, true))) return r;
+    if (a->D != kHeadDim) return fail(LWM_EUNSUPPORTED, "%s: head_dim %ld (only 128)", "attn_prefill_kv8", a->D);
+    if (a->B < 0 || a->Sq < 1 || a->Sk < 1 || a->H <= 0 || a->q_start < 0)
+        return fail(LWM_EINVAL, "%s", "attn_prefill_kv8: bad dimension (B >= 0, Sq >= 1, Sk >= 1, H >= 1, q_start >= 0)");
+    if (!(a->scale > 0.0f)) return fail(LWM_EINVAL, "%s", "attn_prefill_kv8: scale must be > 0");
+    if (!a->k || !a->v || !a->k_scale || !a->v_scale || !a->out_acc || !a->lse_acc)
+        return fail(LWM_EINVAL, "%s", "attn_prefill_kv8: null pointer (k, v, k_scale, v_scale, out_acc, lse_acc)");
+    if (!aligned16(a->k) || !aligned16(a->v) || !aligned16(a->out_acc) || ((a->k_stride_b | a->k_stride_s | a->k_stride_h |
+                                                                          a->v_stride_b | a->v_stride_s | a->v_stride_h) & 15))
+        return fail(LWM_EUNSUPPORTED, "%s", "attn_prefill_kv8: cache rows and out_acc must be 16-byte aligned (pointers and strides)");
+    if ((((uintptr_t)a->k_scale | (uintptr_t)a->v_scale | (uintptr_t)a->lse_acc) & 3))
+        return fail(LWM_EUNSUPPORTED, "%s", "attn_prefill_kv8: scales and lse_acc must be 4-byte aligned");
+    if (a->k_splits < 0 || a->k_splits > 4096) return fail(LWM_EINVAL, "%s", "attn_prefill_kv8: k_splits out of range");
+    if (a->B == 0) return LWM_OK;
+    Kv8PrefillParams p;
+    memset(&p, 0, sizeof(p));
+    p.a.q = (const bf16_t*)a->q.ptr; p.a.q_sb = a->q.stride_b; p.a.q_ss = a->q.stride_s; p.a.q_sh = a->q.stride_h;
+    p.a.out_acc = a->out_acc; p.a.lse_acc = a->lse_acc; p.a.key_valid = a->key_valid;
+    p.a.B = a->B; p.a.H = a->H; p.a.Sq = a->Sq; p.a.Sk = a->Sk;
+    p.a.q_start = a->q_start; p.a.k_start = 0; p.a.q_np = 1; p.a.k_np = 1;
+    p.a.scale = a->scale; p.a.causal = 1; p.a.carry_in = 0; p.a.final_out = 0;
+    p.a.k_splits = a->k_splits > 1 ? a->k_splits : 1;
+    p.k8 = (const uint8_t*)a->k; p.v8 = (const uint8_t*)a->v; p.k_scale = a->k_scale; p.v_scale = a->v_scale;
+    p.k8_sb = a->k_stride_b; p.k8_ss = a->k_stride_s; p.k8_sh = a->k_stride_h;
+    p.v8_sb = a->v_stride_b; p.v8_ss = a->v_stride_s; p.v8_sh = a->v_stride_h;
+    p.ks_sb = a->k_scale_stride_b; p.ks_ss = a->k_scale_stride_s;
+    p.vs_sb = a->v_scale_stride_b; p.vs_ss = a->v_scale_stride_s;
+    p.kv_sb = a->key_valid_stride_b;
+    const long nqt = (p.a.Sq + kFwdBQ - 1) / kFwdBQ;
+    return launch("attn_prefill_kv8", attn_prefill_kv8_kernel, nqt * p.a.H * p.a.B * p.a.k_splits, kFwdThreads, kFwdLdsBytes,
+                  stream, p);
 }
 
 static int check_bwd(const LwmAttnArgs* a) {
@@ -733,9 +771,9 @@ int lwm_sample_tokens(const LwmSampleArgs* a, void* stream) {
 }
 
 const char* lwm_last_error(void) { return lwm::g_err; }
-int lwm_version(void) { return 520; }
+int lwm_version(void) { return 530; }
 int lwm_sizeof(int which) {
-    return which == 0 ? (int)sizeof(LwmAttnArgs) : which == 1 ? (int)sizeof(LwmConvArgs) : which == 2 ? (int)sizeof(LwmRingArgs) : which == 3 ? (int)sizeof(LwmGemvArgs) : which == 4 ? (int)sizeof(LwmSampleArgs) : which == 5 ? (int)sizeof(LwmKv8DecodeArgs) : -1;
+    return which == 0 ? (int)sizeof(LwmAttnArgs) : which == 1 ? (int)sizeof(LwmConvArgs) : which == 2 ? (int)sizeof(LwmRingArgs) : which == 3 ? (int)sizeof(LwmGemvArgs) : which == 4 ? (int)sizeof(LwmSampleArgs) : which == 5 ? (int)sizeof(LwmKv8DecodeArgs) : which == 6 ? (int)sizeof(LwmKv8PrefillArgs) : -1;
 }
 
 }  // extern "C"

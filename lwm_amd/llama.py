@@ -302,6 +302,25 @@ class LLaMAAttention(torch.nn.Module):
                 _ops.kv8_cache_write(cv, vs, xv, dst_row0=0)
                 cache["cache_index"] = Q
                 return out
+            if Q != 1 and cache.get("kv8_blocks"):
+                # a block appended to a live cache (init_cache(chunked_prefill=True)): the decode step's rule -- quantise
+                # your own rows, then read the cache -- for Q rows at once: the same as feeding the tokens one at a time.
+                # lwm_attn_prefill_kv8 dequantises while it stages; no bf16 copy of the cache is made
+                from .kv8 import attn_prefill_kv8
+                _ops.kv8_cache_write(ck, ks, xk, dst_row0=idx)
+                _ops.kv8_cache_write(cv, vs, xv, dst_row0=idx)
+                n = idx + Q
+                kvld = None if attention_mask is None else (attention_mask[:, :n] != 0).to(torch.uint8)
+                o_parts, l_parts = attn_prefill_kv8(xq, ck[:, :n], ks[:, :n], cv[:, :n], vs[:, :n], q_start=idx,
+                                                    k_splits=_pick_splits(B, Q, H, n), key_valid=kvld)
+                cache["cache_index"] = n
+                if o_parts.shape[0] == 1:
+                    # one piece: the partial IS the normalised output, and attn_combine's merge of one piece is the
+                    # identity followed by the rounding to bf16 (the same bits: tests/test_gpu_kv8_prefill.py) -- but a
+                    # workgroup per (row, head) built for hundreds of decode pieces: 1.9 ms for a 4096 x 32 block against
+                    # the cast kernel's HBM time (profiles/r10_kv8_prefill.md)
+                    return _ops.cast_f32_to_bf16(o_parts[0])
+                return _ops.attn_combine(o_parts, l_parts, want_bf16=True)[0]
             if Q != 1:
                 raise NotImplementedError("kv_dtype='fp8' with Q > 1 at cache_index > 0: the 8-bit cache takes a prompt at "
                                           "cache_index 0 and one token per step after it")
@@ -440,12 +459,17 @@ class LLaMAForCausalLM(torch.nn.Module):
             (x2,), ss = gemv_fused(swiglu(gate, up), (mlp.w2,), residual=x2, want_ss=True)
         return x2.reshape(B, 1, d)
 
-    def init_cache(self, batch_size, max_length, device=None, kv_dtype=None):
+    def init_cache(self, batch_size, max_length, device=None, kv_dtype=None, *, chunked_prefill=False):
         """FlaxLLaMAPreTrainedModel.init_cache (lwm/llama.py:810-825): per layer, zeroed
         (B, max_length, H, D) key/value caches and cache_index = 0.
         kv_dtype="fp8" (extension): the 8-bit cache of csrc/attn_decode_kv8.h -- per layer cached_key / cached_value as
         uint8 e4m3fn bytes plus key_scale / value_scale (B, max_length, H) f32: 0.516 of the bytes, held and read per
-        decode step.  bf16 models on one rank; a prompt at cache_index 0, then one token per step."""
+        decode step.  bf16 models on one rank; a prompt at cache_index 0, then one token per step.
+        chunked_prefill=True (with kv_dtype="fp8"): the cache also takes BLOCKS of tokens at cache_index > 0 (chunked
+        prefill, a follow-up turn): such a block is quantised into the cache first and then attends over the quantised
+        rows, its own included -- the decode step's rule, so a block equals its tokens fed one at a time, whereas a block
+        at cache_index 0 sees its own unquantised keys.  Opt-in because of that difference.  The default cache takes blocks
+        anywhere as it is; the flag changes nothing for it."""
         device = device or self.wte.device
         H = self.cfg.num_attention_heads
         D = self.cfg.hidden_size // H
@@ -465,7 +489,8 @@ class LLaMAForCausalLM(torch.nn.Module):
                 raise NotImplementedError(f"kv_dtype='fp8': head_dim {D} (the 8-bit decode kernel is built for 128)")
             q = lambda: torch.zeros(batch_size, max_length, H, D, dtype=torch.uint8, device=device)
             sc = lambda: torch.ones(batch_size, max_length, H, dtype=torch.float32, device=device)
-            return [dict(cached_key=q(), cached_value=q(), key_scale=sc(), value_scale=sc(), cache_index=0) for _ in self.h]
+            mark = dict(kv8_blocks=True) if chunked_prefill else {}
+            return [dict(cached_key=q(), cached_value=q(), key_scale=sc(), value_scale=sc(), cache_index=0, **mark) for _ in self.h]
         # sharded over "sp": each rank holds its contiguous max_length/sp rows (lwm/llama.py:454-467)
         z = lambda: torch.zeros(batch_size, max_length // n_sp, H, D, dtype=self.dtype, device=device)
         return [dict(cached_key=z(), cached_value=z(), cache_index=0) for _ in self.h]
@@ -477,7 +502,7 @@ class LLaMAForCausalLM(torch.nn.Module):
 
     @torch.no_grad()
     def generate(self, input_ids, attention_mask=None, max_new_tokens=16, max_length=None, return_logits=False,
-                 graph=False, kv_dtype=None):
+                 graph=False, kv_dtype=None, prefill_chunk=None):
         """Greedy decoding through the KV cache: prepare_inputs_for_generation /
         update_inputs_for_generation of the reference (lwm/llama.py:1113-1137) + argmax.
         Prefill writes the prompt's keys/values at cache_index 0 and attends over the whole
@@ -490,15 +515,21 @@ class LLaMAForCausalLM(torch.nn.Module):
         issued one by one.  Single-rank only (the cross-rank combine is not captured).
 
         kv_dtype="fp8": the 8-bit KV cache (init_cache); the prompt attends over its own bf16 keys, every later
-        step over the quantised cache.  Works with graph=True."""
+        step over the quantised cache.  Works with graph=True.
+
+        prefill_chunk=N: the prompt goes through the layers in blocks of N tokens (the last may be shorter), so the
+        transient activations of the prefill are bounded by N instead of the prompt length.  With kv_dtype="fp8" the
+        cache is created with chunked_prefill=True: the first block sees its own unquantised keys, every later block the
+        quantised rows (init_cache).  One rank; works with graph=True (the captured step starts after the prefill)."""
         B, S = input_ids.shape
+        check_prefill_chunk(prefill_chunk)
         max_length = max_length or (S + max_new_tokens)
         dev = input_ids.device
         if graph and self.dtype == torch.float32:
             raise NotImplementedError("generate(graph=True) captures the bf16 decode kernels; a float32 model decodes eagerly "
                                       "(graph=False) through the f32 flavour of the attention op")
         # (the default cache through the three-argument call every stand-in model answers)
-        cache = self.init_cache(B, max_length, dev) if kv_dtype is None else self.init_cache(B, max_length, dev, kv_dtype=kv_dtype)
+        cache = self.init_cache(B, max_length, dev, **cache_kwargs(kv_dtype, prefill_chunk))
         ext = torch.ones(B, max_length, dtype=torch.int32, device=dev)
         if attention_mask is not None:
             pos = attention_mask.to(torch.int32).cumsum(-1) - 1
@@ -520,6 +551,12 @@ class LLaMAForCausalLM(torch.nn.Module):
         # prefill (and, without graph, every later step): host-side cache_index
         step_in = input_ids
         n_eager = max_new_tokens if not graph else min(1, max_new_tokens)
+        if prefill_chunk is not None and n_eager > 0:
+            # every block but the last only fills the cache; the last one is the first pass of the loop below
+            for a in range(0, S - prefill_chunk, prefill_chunk):
+                self.hidden_states(input_ids[:, a:a + prefill_chunk], ext, None, pos[:, a:a + prefill_chunk].contiguous(), cache)
+            a = max(0, (S - 1) // prefill_chunk * prefill_chunk)
+            step_in, pos = input_ids[:, a:], pos[:, a:].contiguous()
         for _ in range(n_eager):
             h = self.hidden_states(step_in, ext, None, pos, cache)
             step_in = emit(dense(h[:, -1], head, torch.float32))
@@ -560,6 +597,26 @@ class LLaMAForCausalLM(torch.nn.Module):
         scoring of a short batch on every rank): no collective, each rank gets the whole loss."""
         h = self.hidden_states(input_tokens, attention_mask, segment_ids, position_ids, layout=layout)
         return chunked_lm_head_loss(h, self.lm_head, target_tokens, loss_masks, chunk, sp_sharded=sp_sharded)
+
+def check_prefill_chunk(prefill_chunk):
+    """generate(prefill_chunk=): None, or a block length >= 1 on one rank"""
+    if prefill_chunk is None:
+        return
+    if int(prefill_chunk) != prefill_chunk or prefill_chunk < 1:
+        raise ValueError(f"prefill_chunk={prefill_chunk!r}: None (the whole prompt in one call) or a block length >= 1")
+    if sp_size_rank("sp")[0] > 1:
+        raise NotImplementedError("prefill_chunk with sp > 1: chunked prefill runs on one rank (a sharded prefill block is "
+                                  "already 1/sp of the prompt)")
+
+
+def cache_kwargs(kv_dtype, prefill_chunk=None):
+    """The keyword arguments of init_cache for a generate() call: only what is non-default is passed, so that a stand-in
+    model with the three-argument init_cache keeps working."""
+    kw = {} if kv_dtype is None else dict(kv_dtype=kv_dtype)
+    if kv_dtype == "fp8" and prefill_chunk is not None:
+        kw["chunked_prefill"] = True
+    return kw
+
 
 def hf_rotary_to_interleaved(w_out_in, num_heads):
     """HF-PyTorch LLaMA checkpoints (README.md:74, scripts/sample_pyt.py:8) store wq/wk for the

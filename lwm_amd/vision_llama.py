@@ -9,7 +9,7 @@ from __future__ import annotations
 import torch
 
 from . import ops as _ops
-from .llama import LLaMAConfig, LLaMAForCausalLM, _dense, capture_decode_step
+from .llama import LLaMAConfig, LLaMAForCausalLM, _dense, cache_kwargs, capture_decode_step, check_prefill_chunk
 from .llama_ops import chunked_lm_head_loss, dense
 from .ringattention import sp_size_rank
 
@@ -73,11 +73,14 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
         return 0.5 * (v_loss + t_loss), dict(vision_loss=v_loss, vision_acc=v_acc, text_loss=t_loss, text_acc=t_acc)
 
     # ---- generation (lwm/vision_llama.py:447-745).  Eager, through the KV cache of lwm_amd/llama.py.
-    def _prefill(self, input_ids, vision_masks, attention_mask, max_length, kv_dtype=None):
+    def _prefill(self, input_ids, vision_masks, attention_mask, max_length, kv_dtype=None, prefill_chunk=None):
+        """prefill_chunk=N: the prompt in blocks of N tokens (LLaMAForCausalLM.generate); only the last block's hidden
+        state is kept"""
         B, S = input_ids.shape
         dev = input_ids.device
+        check_prefill_chunk(prefill_chunk)
         # (the default cache through the three-argument call every stand-in model answers)
-        cache = self.init_cache(B, max_length, dev) if kv_dtype is None else self.init_cache(B, max_length, dev, kv_dtype=kv_dtype)
+        cache = self.init_cache(B, max_length, dev, **cache_kwargs(kv_dtype, prefill_chunk))
         ext = torch.ones(B, max_length, dtype=torch.int32, device=dev)
         if attention_mask is not None:
             pos = attention_mask.to(torch.int32).cumsum(-1) - 1          # prepare_inputs_for_generation (:447-466)
@@ -86,7 +89,12 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
             pos = torch.arange(S, dtype=torch.int32, device=dev)[None].expand(B, S)
         pos = pos.clamp_min(0).to(torch.int32).contiguous()
         vm = torch.zeros_like(input_ids, dtype=torch.bool) if vision_masks is None else vision_masks.to(torch.bool)
-        h = self.hidden_states(input_ids, vm, ext, None, pos, cache)
+        if prefill_chunk is None:
+            h = self.hidden_states(input_ids, vm, ext, None, pos, cache)
+        else:
+            for a in range(0, max(S, 1), prefill_chunk):
+                z = a + prefill_chunk
+                h = self.hidden_states(input_ids[:, a:z], vm[:, a:z], ext, None, pos[:, a:z].contiguous(), cache)
         return h[:, -1], cache, ext, (pos[:, -1:] + 1).contiguous()
 
     def _step(self, tok, cache, ext, pos):
@@ -119,7 +127,7 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
 
     def _seeded_decode(self, input_ids, vision_masks, attention_mask, max_length, max_new_tokens, head, *, seed, graph,
                        temperature, top_k, cfg=None, force_period=0, force_token=0, eos=None, pad=0, return_logits=False,
-                       kv_dtype=None):
+                       kv_dtype=None, prefill_chunk=None):
         """Decoding with every token chosen by ops.sample_tokens (csrc/sample.h) from the Philox stream of `seed`: the
         sampler also writes the next step's input ids, the output column and the done flags, so no step waits for the
         host.  graph=True: the one-token step -- layers, head, sampler, cache index -- is captured ONCE in a hipGraph
@@ -137,7 +145,7 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
             if sp_size_rank("sp")[0] > 1 or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
                 raise NotImplementedError("graph=True is single-rank (the cross-rank combine is not captured)")
         max_length = max_length or (S + max_new_tokens)
-        h, cache, ext, pos = self._prefill(input_ids, vision_masks, attention_mask, max_length, kv_dtype)
+        h, cache, ext, pos = self._prefill(input_ids, vision_masks, attention_mask, max_length, kv_dtype, prefill_chunk)
         seq = torch.full((B, max_new_tokens), int(pad), dtype=torch.int64, device=dev)
         tok = torch.empty((rows, 1), dtype=torch.int64, device=dev)
         done = None if eos is None else torch.zeros(B, dtype=torch.uint8, device=dev)
@@ -189,7 +197,7 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
     @torch.no_grad()
     def generate(self, input_ids, vision_masks=None, attention_mask=None, max_new_tokens=16, max_length=None,
                  temperature=1.0, top_k=None, do_sample=False, eos_token_id=None, pad_token_id=0, generator=None,
-                 seed=None, graph=False, return_logits=False, kv_dtype=None):
+                 seed=None, graph=False, return_logits=False, kv_dtype=None, prefill_chunk=None):
         """Text continuation of a (left-padded) vision-language prompt -- what lwm/vision_chat.py:205-227
         runs with sample_mode='text': prefill over both embedding tables, then one token at a time
         through the text head.  Returns the NEW tokens (B, max_new_tokens), pad after eos (and the f32 logits of
@@ -199,7 +207,8 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
         token drawn on the device by ops.sample_tokens from the Philox stream of `seed` (bf16 or float32 models);
         seed= with graph=True = the same one-token step captured once in a hipGraph and replayed (bf16, one rank).
         With a seed the loop reads `done` back every DONE_CHECK_EVERY tokens instead of after every token.
-        kv_dtype="fp8": the 8-bit KV cache (LLaMAModel.init_cache), on every one of these routes."""
+        kv_dtype="fp8": the 8-bit KV cache (LLaMAModel.init_cache), on every one of these routes.  prefill_chunk=N: the
+        prompt in blocks of N tokens (LLaMAForCausalLM.generate), on every one of these routes too."""
         if self.cfg.sample_mode != "text":
             raise ValueError("generate() decodes text: set sample_mode='text' (scripts/run_vision_chat.sh)")
         if seed is not None or graph:
@@ -208,12 +217,12 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
                                               self.lm_head, seed=seed, graph=graph,
                                               temperature=temperature if do_sample else 0.0, top_k=top_k,
                                               eos=eos_token_id, pad=pad_token_id, return_logits=return_logits,
-                                              kv_dtype=kv_dtype)
+                                              kv_dtype=kv_dtype, prefill_chunk=prefill_chunk)
             out = out.to(input_ids.dtype)
             return (out, logits) if return_logits else out
         B, S = input_ids.shape
         max_length = max_length or (S + max_new_tokens)
-        h, cache, ext, pos = self._prefill(input_ids, vision_masks, attention_mask, max_length, kv_dtype)
+        h, cache, ext, pos = self._prefill(input_ids, vision_masks, attention_mask, max_length, kv_dtype, prefill_chunk)
         head = self.lm_head        # (f32 logits from the bf16 kernel: llama_ops.dense)
         out = torch.full((B, max_new_tokens), int(pad_token_id), dtype=input_ids.dtype, device=input_ids.device)
         done = torch.zeros(B, dtype=torch.bool, device=input_ids.device)
@@ -235,7 +244,7 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
     @torch.no_grad()
     def generate_vision(self, input_ids, cfg_scales, attention_mask=None, vision_masks=None, max_new_tokens=257,
                         temperature=1.0, top_k=None, generator=None, max_length=None, seed=None, graph=False,
-                        return_logits=False, kv_dtype=None):
+                        return_logits=False, kv_dtype=None, prefill_chunk=None):
         """FlaxVideoLLaMAForCausalLM.generate_vision / _sample_vision (lwm/vision_llama.py:476-745):
         the batch holds the conditional prompts followed by the same number of unconditional ones;
         logits = uncond + cfg * (cond - uncond) over the VISION head (sample_mode='vision'), top-k /
@@ -245,7 +254,8 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
 
         Sampling as generate(): generator= = the torch sampler, eager; seed= = ops.sample_tokens on the device, which
         also mixes the halves, forces the end-of-frame code and feeds both halves; seed= with graph=True = that step
-        captured once in a hipGraph and replayed (bf16, one rank).  kv_dtype="fp8": the 8-bit KV cache."""
+        captured once in a hipGraph and replayed (bf16, one rank).  kv_dtype="fp8": the 8-bit KV cache; prefill_chunk=N: the
+        prompt in blocks of N tokens (LLaMAForCausalLM.generate)."""
         if self.cfg.sample_mode != "vision":
             raise ValueError("generate_vision() needs sample_mode='vision' (scripts/run_sample_image.sh)")
         B2, S = input_ids.shape
@@ -259,11 +269,11 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
                                               self._vision_kernel().contiguous(), seed=seed, graph=graph,
                                               temperature=temperature, top_k=top_k, cfg=cfg.reshape(B).contiguous(),
                                               force_period=257, force_token=8192, return_logits=return_logits,
-                                              kv_dtype=kv_dtype)
+                                              kv_dtype=kv_dtype, prefill_chunk=prefill_chunk)
             out = out.to(input_ids.dtype)
             return (out, logits) if return_logits else out
         max_length = max_length or (S + max_new_tokens)
-        h, cache, ext, pos = self._prefill(input_ids, vision_masks, attention_mask, max_length, kv_dtype)
+        h, cache, ext, pos = self._prefill(input_ids, vision_masks, attention_mask, max_length, kv_dtype, prefill_chunk)
         head = self._vision_kernel().contiguous()
         out = torch.empty((B, max_new_tokens), dtype=input_ids.dtype, device=input_ids.device)
         logits_out = []
