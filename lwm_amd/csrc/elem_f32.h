@@ -254,10 +254,11 @@ LWM_KERNEL(kCeThreads) void softmax_ce_f32_kernel(CeF32Params p) {
         const float wgt = p.weight ? p.weight[row] : 1.0f;
         if (tid == 0) {
             const float lt = (tg >= 0 && tg < p.V) ? lr[tg] : 0.0f;
-            p.nll[row] = (mx + logf(tot)) - lt;
+            p.nll[row] = logf(tot) - (lt - mx);      // (the order of jax.nn.log_softmax, see softmax_ce_kernel)
             if (p.correct) p.correct[row] = (amax == tg) ? 1 : 0;
         }
         if (p.dlogits) {
+            const bool dead = wgt == 0.0f;      // weight 0: an exact 0 gradient whatever the row holds (see softmax_ce_kernel)
             const float s = wgt / tot;
 #pragma unroll
             for (int k = 0; k < 16; ++k) {
@@ -265,7 +266,7 @@ LWM_KERNEL(kCeThreads) void softmax_ce_f32_kernel(CeF32Params p) {
                 if (v < nv) {
                     f32x4 o;
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) o[j] = x[k][j] * s - (v * 4 + j == tg ? wgt : 0.0f);
+                    for (int j = 0; j < 4; ++j) o[j] = dead ? 0.0f : x[k][j] * s - (v * 4 + j == tg ? wgt : 0.0f);
                     global_store_f32x4(p.dlogits + row * p.V + v * 4, o);
                 }
             }

@@ -328,10 +328,14 @@ LWM_KERNEL(kCeThreads) void softmax_ce_kernel(CeParams p) {
         const float wgt = p.weight ? p.weight[row] : 1.0f;
         if (tid == 0) {
             const float lt = (tg >= 0 && tg < p.V) ? (float)lr[tg] : 0.0f;
-            p.nll[row] = (mx + logf(tot)) - lt;
+            // log sum exp(x - mx) - (x_t - mx), the order of jax.nn.log_softmax: (mx + log tot) - x_t would round at ulp(mx)
+            p.nll[row] = logf(tot) - (lt - mx);
             if (p.correct) p.correct[row] = (amax == tg) ? 1 : 0;
         }
         if (p.dlogits) {
+            // a row of weight 0 (valid == 0) gets an exact 0 gradient whatever its logits hold: NaN or Inf in a masked row
+            // must not reach the backward (tux selects with where(valid > 0, ., 0))
+            const bool dead = wgt == 0.0f;
             const float s = wgt / tot;
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
@@ -343,7 +347,7 @@ LWM_KERNEL(kCeThreads) void softmax_ce_kernel(CeParams p) {
                         const int i0 = v * 8 + 2 * j;
                         const float g0 = x[k][2 * j] * s - (i0 == tg ? wgt : 0.0f);
                         const float g1 = x[k][2 * j + 1] * s - (i0 + 1 == tg ? wgt : 0.0f);
-                        o[j] = pack_bf16x2(g0, g1);
+                        o[j] = dead ? 0u : pack_bf16x2(g0, g1);
                     }
                     global_store_b128(p.dlogits + row * p.V + v * 8, o);
                 }

@@ -220,7 +220,9 @@ class _CrossEntropy(torch.autograd.Function):
         v, w = _row_weights(valid, B, S, logits.device, sp_sharded)
         nll, correct, dl = _softmax_ce(logits.reshape(B * S, V), tokens.reshape(-1).to(torch.int32).contiguous(),
                                        w.reshape(-1), logits.requires_grad)
-        loss = (nll.reshape(B, S) * w).sum()
+        # select, not multiply: a masked row may hold NaN / Inf logits (tux: where(valid > 0, log p, 0)); the kernel writes an
+        # exact 0 gradient for such a row
+        loss = torch.where(w > 0, nll.reshape(B, S) * w, 0.0).sum()
         acc = (correct.reshape(B, S).to(torch.float32) * w).sum()
         ctx.save_for_backward(dl)
         ctx.shape = (B, S, V)
@@ -274,7 +276,7 @@ class _ChunkedHeadLoss(torch.autograd.Function):
             nll, correct, dl = _softmax_ce(logits, tok[:, s0:s1].reshape(-1).contiguous(),
                                            w[:, s0:s1].reshape(-1).contiguous(), need)
             wc = w[:, s0:s1].reshape(-1)
-            loss += (nll * wc).sum()
+            loss += torch.where(wc > 0, nll * wc, 0.0).sum()     # (as _CrossEntropy: a masked row may hold NaN / Inf)
             acc += (correct.to(torch.float32) * wc).sum()
             if need:
                 dh[:, s0:s1] = (dl @ kb.t()).reshape(B, s1 - s0, Dm)
