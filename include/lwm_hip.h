@@ -569,6 +569,62 @@ typedef struct LwmSampleArgs {
 } LwmSampleArgs;
 int lwm_sample_tokens(const LwmSampleArgs* args, void* stream);
 
+/* ------------------------------------------------------------------ fused AdamW (lwm_version() >= 540)
+ * The optimiser phase of a training step over a LIST of tensors, one launch per phase: gradient clipping by the global
+ * norm (torch.nn.utils.clip_grad_norm_) and AdamW with decoupled weight decay (torch.optim.AdamW) on f32 master weights
+ * and f32 moments, with an optional bf16 working copy of each tensor written in the same pass.  Two tables in DEVICE
+ * memory drive it:
+ *   tensors  one LwmAdamWTensor per tensor.  Every base is 16-byte aligned.  bias_corr1 = 1 - beta1^t and
+ *            sqrt_bias_corr2 = sqrt(1 - beta2^t) are computed by the caller in double from THAT tensor's step count t
+ *            (torch counts steps per parameter: one that had no gradient in some step lags behind);
+ *   chunks   [n_chunks][2] int32: (tensor, chunk of that tensor).  Chunk k of a tensor is its elements
+ *            [k * lwm_adamw_chunk(), (k + 1) * lwm_adamw_chunk()), the last one cut at numel; every chunk of every
+ *            tensor is listed once, in any order.  An entry that names no element is skipped.
+ * lwm_adamw_grad_norm:  grad_partials[c] = sum of g^2 over chunk c in f64; then one workgroup sums the partials in a
+ *            fixed order in f64 and writes norms[0] = (float)sqrt(sum) and the clipping coefficient
+ *            norms[1] = min(1, max_norm / (norms[0] + 1e-6f)) in f32 (1 when max_norm <= 0).
+ * lwm_adamw_step:  reads the coefficient from norms[1] (no host round trip), then per element, in f32, every
+ *            operation rounded on its own:
+ *              g = g * coef;  m = m * beta1 + g * (1 - beta1);  v = v * beta2 + (g * g) * (1 - beta2)
+ *              den = sqrt(v) / sqrt_bias_corr2 + eps
+ *              p = p * (1 - lr * weight_decay)      (tensors with decay != 0)
+ *              p = p - (lr / bias_corr1) * (m / den)
+ *            stores p, m, v and, where copy_bf16 is given, p rounded to bf16 (nearest even); param_partials[c] = sum of
+ *            the NEW p^2 over chunk c in f64, and one workgroup writes norms[2] = the parameter norm after the update.
+ *            beta1, beta2, 1 - beta1, 1 - beta2, 1 - lr * weight_decay, lr and eps are rounded to f32 once, from the
+ *            doubles below; lr / bias_corr1 is one f32 division per tensor.
+ * No floating-point atomics and no order that depends on the launch shape: the same inputs give the same bits.
+ * Non-finite gradients are not detected; the arithmetic propagates them. */
+typedef struct LwmAdamWTensor {
+    float* master;             /* [numel] f32: the parameter */
+    const void* grad;          /* [numel] bf16 (grad_bf16 != 0) or f32 */
+    float* exp_avg;            /* [numel] f32 */
+    float* exp_avg_sq;         /* [numel] f32 */
+    void* copy_bf16;           /* [numel] bf16 working copy, or NULL */
+    int64_t numel;
+    int32_t grad_bf16;
+    int32_t decay;             /* != 0: weight decay applies to this tensor */
+    float bias_corr1;
+    float sqrt_bias_corr2;
+} LwmAdamWTensor;
+
+typedef struct LwmAdamWArgs {
+    const LwmAdamWTensor* tensors;   /* DEVICE [n_tensors] */
+    const int32_t* chunks;           /* DEVICE [n_chunks][2] */
+    int32_t n_tensors, n_chunks;
+    double lr, beta1, beta2, eps, weight_decay;
+    double max_norm;                 /* <= 0: no clipping */
+    double* grad_partials;           /* DEVICE f64 workspace of phase A */
+    int64_t grad_partials_len;       /* its length in elements, >= n_chunks */
+    double* param_partials;          /* DEVICE f64 workspace of phase B */
+    int64_t param_partials_len;
+    float* norms;                    /* DEVICE [3] f32: gradient norm, clipping coefficient, parameter norm */
+} LwmAdamWArgs;
+int lwm_adamw_grad_norm(const LwmAdamWArgs* args, void* stream);
+int lwm_adamw_step(const LwmAdamWArgs* args, void* stream);
+/* elements of one chunk of the chunk table (a constant of the library) */
+int lwm_adamw_chunk(void);
+
 /* ------------------------------------------------------------------ VQGAN
  * Primitives of the video tokeniser, lwm/vqgan.py.  All tensors are f32, NHWC,
  * dense; results are bit-exact with oracle/vqgan_ref.c (exact-f32 MFMA, fixed
@@ -619,7 +675,8 @@ int lwm_vq_gather_f32(const float* codebook, const int32_t* idx, const float* z,
 const char* lwm_last_error(void);
 int lwm_version(void);
 /* sizeof(LwmAttnArgs) (which = 0) / sizeof(LwmConvArgs) (1) / sizeof(LwmRingArgs) (2) / sizeof(LwmGemvArgs) (3) /
- * sizeof(LwmSampleArgs) (4) / sizeof(LwmKv8DecodeArgs) (5) / sizeof(LwmKv8PrefillArgs) (6) as compiled into the library:
+ * sizeof(LwmSampleArgs) (4) / sizeof(LwmKv8DecodeArgs) (5) / sizeof(LwmKv8PrefillArgs) (6) / sizeof(LwmAdamWArgs) (7) as
+ * sizeof(LwmAdamWTensor) (8: an element of a device table that the caller lays out) as compiled into the library:
  * lets a foreign-language binding verify its struct mirror at load time. */
 int lwm_sizeof(int which);
 

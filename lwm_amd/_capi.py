@@ -126,6 +126,26 @@ class LwmSampleArgs(C.Structure):
     ]
 
 
+class LwmAdamWTensor(C.Structure):
+    """one entry of the DEVICE tensor table of the fused AdamW (built on the host, copied over)"""
+    _fields_ = [
+        ("master", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+        ("copy_bf16", C.c_void_p), ("numel", C.c_int64), ("grad_bf16", C.c_int32), ("decay", C.c_int32),
+        ("bias_corr1", C.c_float), ("sqrt_bias_corr2", C.c_float),
+    ]
+
+
+class LwmAdamWArgs(C.Structure):
+    _fields_ = [
+        ("tensors", C.c_void_p), ("chunks", C.c_void_p), ("n_tensors", C.c_int32), ("n_chunks", C.c_int32),
+        ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
+        ("max_norm", C.c_double),
+        ("grad_partials", C.c_void_p), ("grad_partials_len", C.c_int64),
+        ("param_partials", C.c_void_p), ("param_partials_len", C.c_int64),
+        ("norms", C.c_void_p),
+    ]
+
+
 RING_GROUP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
 RING_SEND_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p)
 
@@ -219,6 +239,9 @@ PROTOTYPES = {
                                       C.c_int32, C.c_int32, C.c_void_p]),
     "lwm_gemv_fused_bf16": (C.c_int, [C.POINTER(LwmGemvArgs), C.c_void_p]),
     "lwm_sample_tokens": (C.c_int, [C.POINTER(LwmSampleArgs), C.c_void_p]),
+    "lwm_adamw_grad_norm": (C.c_int, [C.POINTER(LwmAdamWArgs), C.c_void_p]),
+    "lwm_adamw_step": (C.c_int, [C.POINTER(LwmAdamWArgs), C.c_void_p]),
+    "lwm_adamw_chunk": (C.c_int, []),
     "lwm_cast_f32_to_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "lwm_sum_f32_to_bf16": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "lwm_conv2d_nhwc_f32": (C.c_int, [C.POINTER(LwmConvArgs), C.c_void_p]),
@@ -242,7 +265,7 @@ def bind(lib):
         fn.restype = res
         fn.argtypes = args
     for which, cls in ((0, LwmAttnArgs), (1, LwmConvArgs), (2, LwmRingArgs), (4, LwmSampleArgs), (5, LwmKv8DecodeArgs),
-                       (6, LwmKv8PrefillArgs)):
+                       (6, LwmKv8PrefillArgs), (7, LwmAdamWArgs), (8, LwmAdamWTensor)):
         if lib.lwm_sizeof(which) != C.sizeof(cls):
             raise ImportError(f"{cls.__name__}: ctypes mirror is {C.sizeof(cls)} bytes, library has "
                               f"{lib.lwm_sizeof(which)} (include/lwm_hip.h and lwm_amd/_capi.py out of step)")

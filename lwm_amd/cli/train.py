@@ -13,7 +13,13 @@ exchange is driven by the C-ABI ring driver (RCCL on a side stream) when the job
 reference's set, for tests and diagnosis: --lwm_dump_grads=<file> (rank 0 saves the batch, the parameters, the loss
 and every gradient of the last step) and --lwm_balance_report (the attention launches of every sp rank timed in turn on
 this rank's GPU; --lwm_balance_seq=<S> / --lwm_balance_heads=<H> time another sequence length / head count than the
-job's: a debug model's 2 heads make 64 workgroups for 256 CUs, and the longest workgroup, not the work, sets the time)."""
+job's: a debug model's 2 heads make 64 workgroups for 256 CUs, and the longest workgroup, not the work, sets the time).
+
+--lwm_fused_optimizer (off by default: without it nothing changes) replaces clip_grad_norm_ + torch.optim.AdamW by
+lwm_amd.optim.FusedAdamW: the same --optimizer.adamw_optimizer.* values, weight decay on every parameter (the reference's
+get_weight_decay_exclusions() is empty, lwm/llama.py:286-287), f32 master weights and moments under bf16 parameters (the
+reference's param_dtype=float32), four HIP launches for clipping + update, and `gradient_norm` / `param_norm` in every
+record (lwm/train.py:216-222).  It runs on the gradients as they are after the all-reduce and adds no communication."""
 from __future__ import annotations
 
 import math
@@ -29,7 +35,8 @@ DEFAULTS = dict(
     modality="text", use_data_sharded_loader=True, seed=42, mesh_dim="1,-1,1,1", dtype="bf16", total_steps=10000,
     load_llama_config="", update_llama_config="", load_checkpoint="", load_dataset_state="", log_freq=50,
     save_model_freq=0, save_milestone_freq=0, eval_steps=0, tokenizer="LargeWorldModel/LWM-Text-1M",
-    log_all_worker=False, autoresume=False, lwm_dump_grads="", lwm_balance_report=False, lwm_balance_seq=0, lwm_balance_heads=0)
+    log_all_worker=False, autoresume=False, lwm_dump_grads="", lwm_balance_report=False, lwm_balance_seq=0, lwm_balance_heads=0,
+    lwm_fused_optimizer=False)
 GROUPS = ("train_dataset", "eval_dataset", "optimizer", "checkpointer", "llama", "logger", "jax_distributed")
 
 
@@ -80,9 +87,16 @@ def main(argv=None):
     if F.optimizer.get("type", "adamw") != "adamw":
         raise SystemExit(f"--optimizer.type={F.optimizer.get('type')!r}: only adamw")
     accum = int(F.optimizer.get("accumulate_gradient_steps", 1))
-    opt = torch.optim.AdamW(model.parameters(), lr=lr_at(0, opt_cfg), betas=(float(opt_cfg.get("b1", 0.9)),
-                            float(opt_cfg.get("b2", 0.95))), weight_decay=float(opt_cfg.get("weight_decay", 1e-4)))
     clip = float(opt_cfg.get("clip_gradient", 1.0))
+    adamw = dict(lr=lr_at(0, opt_cfg), betas=(float(opt_cfg.get("b1", 0.9)), float(opt_cfg.get("b2", 0.95))),
+                 weight_decay=float(opt_cfg.get("weight_decay", 1e-4)))
+    fused = bool(F.lwm_fused_optimizer)
+    if fused:
+        from ..optim import FusedAdamW
+        opt = FusedAdamW(model.parameters(), max_grad_norm=clip, **adamw)
+        C.note("optimizer: FusedAdamW (HIP clipping + AdamW on f32 master weights and moments)")
+    else:
+        opt = torch.optim.AdamW(model.parameters(), **adamw)
     import torch.distributed as dist
     from ..ringattention import sp_all_reduce_sum, sp_layout, sp_shard
     multi = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
@@ -143,13 +157,16 @@ def main(argv=None):
                         "params": {n: p.detach().float().cpu() for n, p in model.named_parameters()},
                         "grads": {n: p.grad.detach().float().cpu() for n, p in model.named_parameters() if p.grad is not None}},
                        F.lwm_dump_grads)
-        torch.nn.utils.clip_grad_norm_(model.parameters(), clip)
+        if not fused:
+            torch.nn.utils.clip_grad_norm_(model.parameters(), clip)
         opt.step()
         opt.zero_grad(set_to_none=True)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         rec = dict(step=step, loss=float(loss.detach()), learning_rate=lr_at(step, opt_cfg), tokens_per_s=batch * seq * accum / dt,
                    **{k: float(v.detach()) if hasattr(v, "detach") else float(v) for k, v in metrics.items()})
+        if fused:
+            rec.update(gradient_norm=float(opt.grad_norm), param_norm=float(opt.param_norm))
         history.append(rec)
         if F.log_freq and step % int(F.log_freq) == 0 and (world_rank == 0 or F.log_all_worker):
             print(rec, flush=True)

@@ -4,6 +4,7 @@
 // Expects: wave_ops.h, launch.h, attn_common.h, attn_fwd.h, attn_fwd64.h, attn_bwd.h, attn_bwd64.h,
 // misc_kernels.h and "lwm_hip.h" already included.
 #include "sample.h"
+#include "optim.h"
 #include "attn_decode_kv8.h"
 #include "attn_prefill_kv8.h"
 
@@ -770,10 +771,64 @@ int lwm_sample_tokens(const LwmSampleArgs* a, void* stream) {
     return launch("sample_tokens", sample_kernel, B, kSampleThreads, kSampleLdsBytes, stream, p);
 }
 
+// the arguments both AdamW entries share, checked before any launch; -> the kernel's parameters
+static int adamw_params(const char* name, const LwmAdamWArgs* a, lwm::AdamWParams* p) {
+    using namespace lwm;
+    if (!a) return fail(LWM_EINVAL, "%s: args is null", name);
+    if (a->n_tensors < 0 || a->n_chunks < 0) return fail(LWM_EINVAL, "%s: n_tensors = %ld, n_chunks = %ld (need >= 0)", name, (long)a->n_tensors, (long)a->n_chunks);
+    if (a->n_chunks > 0 && (!a->tensors || !a->chunks || a->n_tensors == 0))
+        return fail(LWM_EINVAL, "%s: null tensor table or chunk table", name);
+    if (!(a->lr >= 0.0) || !isfinite(a->lr)) return fail(LWM_EINVAL, "%s: lr must be finite and >= 0", name);
+    if (!(a->eps >= 0.0) || !isfinite(a->eps)) return fail(LWM_EINVAL, "%s: eps must be finite and >= 0", name);
+    if (!(a->weight_decay >= 0.0) || !isfinite(a->weight_decay)) return fail(LWM_EINVAL, "%s: weight_decay must be finite and >= 0", name);
+    if (!(a->beta1 >= 0.0 && a->beta1 < 1.0) || !(a->beta2 >= 0.0 && a->beta2 < 1.0))
+        return fail(LWM_EINVAL, "%s: beta1 and beta2 must lie in [0, 1)", name);
+    if (a->max_norm != a->max_norm) return fail(LWM_EINVAL, "%s: max_norm is NaN", name);
+    if (!a->norms || !a->grad_partials || !a->param_partials) return fail(LWM_EINVAL, "%s: null norms or partials workspace", name);
+    if (a->grad_partials_len < a->n_chunks || a->param_partials_len < a->n_chunks)
+        return fail(LWM_EINVAL, "%s: a partials workspace is smaller than the chunk count %ld", name, (long)a->n_chunks);
+    if ((((uintptr_t)a->tensors | (uintptr_t)a->grad_partials | (uintptr_t)a->param_partials) & 7) ||
+        (((uintptr_t)a->chunks | (uintptr_t)a->norms) & 3))
+        return fail(LWM_EINVAL, "%s: misaligned pointer (tensors, partials: 8 bytes; chunks, norms: 4)", name);
+    memset(p, 0, sizeof(*p));
+    p->tensors = a->tensors; p->chunks = a->chunks; p->n_tensors = a->n_tensors; p->n_chunks = a->n_chunks;
+    p->norms = a->norms;
+    p->lr = (float)a->lr; p->beta1 = (float)a->beta1; p->om_beta1 = (float)(1.0 - a->beta1);
+    p->beta2 = (float)a->beta2; p->om_beta2 = (float)(1.0 - a->beta2); p->eps = (float)a->eps;
+    p->decay = (float)(1.0 - a->lr * a->weight_decay);
+    return 0;
+}
+
+static long adamw_blocks(int32_t n_chunks) { return n_chunks < lwm::kAdamWMaxBlocks ? n_chunks : lwm::kAdamWMaxBlocks; }
+
+int lwm_adamw_grad_norm(const LwmAdamWArgs* a, void* stream) {
+    using namespace lwm;
+    AdamWParams p;
+    int r;
+    if ((r = adamw_params("adamw_grad_norm", a, &p))) return r;
+    p.partials = a->grad_partials;
+    if ((r = launch("adamw_grad_sq", adamw_grad_sq_kernel, adamw_blocks(p.n_chunks), kAdamWThreads, kAdamWLdsBytes, stream, p))) return r;
+    return launch("adamw_grad_norm", adamw_norm_kernel, 1, kNormThreads, kAdamWLdsBytes, stream, (const double*)a->grad_partials,
+                  p.n_chunks, a->norms, (int32_t)0, (float)a->max_norm);
+}
+
+int lwm_adamw_step(const LwmAdamWArgs* a, void* stream) {
+    using namespace lwm;
+    AdamWParams p;
+    int r;
+    if ((r = adamw_params("adamw_step", a, &p))) return r;
+    p.partials = a->param_partials;
+    if ((r = launch("adamw_update", adamw_update_kernel, adamw_blocks(p.n_chunks), kAdamWThreads, kAdamWLdsBytes, stream, p))) return r;
+    return launch("adamw_param_norm", adamw_norm_kernel, 1, kNormThreads, kAdamWLdsBytes, stream, (const double*)a->param_partials,
+                  p.n_chunks, a->norms, (int32_t)2, 0.0f);
+}
+
+int lwm_adamw_chunk(void) { return lwm::kAdamWChunk; }
+
 const char* lwm_last_error(void) { return lwm::g_err; }
-int lwm_version(void) { return 530; }
+int lwm_version(void) { return 540; }
 int lwm_sizeof(int which) {
-    return which == 0 ? (int)sizeof(LwmAttnArgs) : which == 1 ? (int)sizeof(LwmConvArgs) : which == 2 ? (int)sizeof(LwmRingArgs) : which == 3 ? (int)sizeof(LwmGemvArgs) : which == 4 ? (int)sizeof(LwmSampleArgs) : which == 5 ? (int)sizeof(LwmKv8DecodeArgs) : which == 6 ? (int)sizeof(LwmKv8PrefillArgs) : -1;
+    return which == 0 ? (int)sizeof(LwmAttnArgs) : which == 1 ? (int)sizeof(LwmConvArgs) : which == 2 ? (int)sizeof(LwmRingArgs) : which == 3 ? (int)sizeof(LwmGemvArgs) : which == 4 ? (int)sizeof(LwmSampleArgs) : which == 5 ? (int)sizeof(LwmKv8DecodeArgs) : which == 6 ? (int)sizeof(LwmKv8PrefillArgs) : which == 7 ? (int)sizeof(LwmAdamWArgs) : which == 8 ? (int)sizeof(LwmAdamWTensor) : -1;
 }
 
 }  // extern "C"
