@@ -522,6 +522,39 @@ typedef struct LwmGemvArgs {
 } LwmGemvArgs;
 int lwm_gemv_fused_bf16(const LwmGemvArgs* args, void* stream);
 
+/* ------------------------------------------------------------------ 8-bit decode weights (lwm_version() >= 550)
+ * The projections of a cached-decode step stream every weight once per token; an 8-bit copy of a kernel is 0.516 of the
+ * bytes.  A bf16 kernel W of shape [K, N], row-major as the GEMV reads it, becomes
+ *   q      uint8 [K, N]               OCP e4m3fn bit patterns (1 sign, 4 exponent bits with bias 7, 3 mantissa bits;
+ *                                     exponent 0 = subnormal m * 2^-9; 0x7f / 0xff = NaN), the same layout;
+ *   scale  f32   [ceil(K/128), N]     one scale per group of 128 rows of K and per column -- the group is the K tile of
+ *                                     one GEMV partial sum.
+ * Quantising one group of one column: amax = max |w| over the group's rows that exist (the last group of a K that is
+ * no multiple of 128 is shorter); s = the smallest power of two with amax / s <= 448, clamped to [2^-126, 2^127], and
+ * s = 1 when amax == 0; q = e4m3(w / s), round to nearest even.  w / s is exact and |w / s| <= 448: nothing saturates,
+ * and the bytes 0x7f / 0xff are never written.  Non-finite weights (Inf, NaN) are NOT supported: their group's scale and
+ * bytes are unspecified.  The GEMV does not sanitise NaN bytes: they propagate.
+ * lwm_w8_quantise: one pass over w [K, N] bf16 -> q, scale and `rounded` [K, N] bf16 = bf16(e4m3(q) * s), the value
+ *   the bytes stand for (`rounded` may be w itself: rounding in place).  K % 32 == 0, K <= 12288, N % 8 == 0; every
+ *   pointer 16-byte aligned.  No atomics: the same input gives the same bits.
+ * lwm_gemv_fused_w8: lwm_gemv_fused_bf16 with w[i] = the bytes and w_scale[i] = the scales of kernel i; every other
+ *   field means what it means in LwmGemvArgs (rows <= 4, K % 32 == 0, K <= 12288; N[i] % 8 == 0; workspace of the sum
+ *   of lwm_gemv_workspace_bytes(rows, K, N[i]) bytes).  Same K partition, same order of every sum as the bf16 entry; the
+ *   scale multiplies each partial sum once.  Exactness domain: e4m3(q) * s has 4 significant bits and is a bf16 value
+ *   whenever it is a normal number, and with power-of-two scales and neither overflow nor underflow in the partial sums
+ *   (scales between 2^-40 and 2^40 and activations of ordinary size are well inside) the results -- outputs and workspace
+ *   partials -- are BIT FOR BIT those of lwm_gemv_fused_bf16 on the `rounded` weights. */
+int lwm_w8_quantise(const void* w, void* q, float* scale, void* rounded, int32_t K, int32_t N, void* stream);
+typedef struct LwmGemvW8Args {
+    const void* x; int64_t ldx; int32_t nmat; int32_t rows, K;
+    const void* w[3]; const float* w_scale[3]; void* y[3]; int64_t ldy[3]; float* y_f32[3]; int32_t N[3];
+    void* workspace;
+    const void* norm_weight; const float* ss_in; int32_t ss_n; float eps;
+    const void* residual[3]; int64_t ldres[3];
+    float* ss_out;
+} LwmGemvW8Args;
+int lwm_gemv_fused_w8(const LwmGemvW8Args* args, void* stream);
+
 /* tux.cross_entropy_loss_and_accuracy as used at lwm/train.py:177-181, :192-201, per row of
  * bf16 logits [rows, V] (V % 8 == 0, V <= 32768): nll[r] = logsumexp(row) - row[target[r]] in
  * f32; correct[r] = (first argmax == target[r]) (may be NULL); and, if dlogits != NULL, the
@@ -676,7 +709,8 @@ const char* lwm_last_error(void);
 int lwm_version(void);
 /* sizeof(LwmAttnArgs) (which = 0) / sizeof(LwmConvArgs) (1) / sizeof(LwmRingArgs) (2) / sizeof(LwmGemvArgs) (3) /
  * sizeof(LwmSampleArgs) (4) / sizeof(LwmKv8DecodeArgs) (5) / sizeof(LwmKv8PrefillArgs) (6) / sizeof(LwmAdamWArgs) (7) as
- * sizeof(LwmAdamWTensor) (8: an element of a device table that the caller lays out) as compiled into the library:
+ * sizeof(LwmAdamWTensor) (8: an element of a device table that the caller lays out) / sizeof(LwmGemvW8Args) (9) as
+ * compiled into the library:
  * lets a foreign-language binding verify its struct mirror at load time. */
 int lwm_sizeof(int which);
 

@@ -85,6 +85,19 @@ class LwmGemvArgs(C.Structure):
     ]
 
 
+class LwmGemvW8Args(C.Structure):
+    """LwmGemvArgs with w[i] as e4m3 bytes plus their scale tables"""
+    _fields_ = [
+        ("x", C.c_void_p), ("ldx", C.c_int64), ("nmat", C.c_int32), ("rows", C.c_int32), ("K", C.c_int32),
+        ("w", C.c_void_p * 3), ("w_scale", C.c_void_p * 3), ("y", C.c_void_p * 3), ("ldy", C.c_int64 * 3),
+        ("y_f32", C.c_void_p * 3), ("N", C.c_int32 * 3),
+        ("workspace", C.c_void_p),
+        ("norm_weight", C.c_void_p), ("ss_in", C.c_void_p), ("ss_n", C.c_int32), ("eps", C.c_float),
+        ("residual", C.c_void_p * 3), ("ldres", C.c_int64 * 3),
+        ("ss_out", C.c_void_p),
+    ]
+
+
 class LwmKv8DecodeArgs(C.Structure):
     _fields_ = [
         ("q", LwmTensor4), ("k", C.c_void_p), ("v", C.c_void_p),
@@ -238,6 +251,8 @@ PROTOTYPES = {
                                       C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_void_p,
                                       C.c_int32, C.c_int32, C.c_void_p]),
     "lwm_gemv_fused_bf16": (C.c_int, [C.POINTER(LwmGemvArgs), C.c_void_p]),
+    "lwm_w8_quantise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "lwm_gemv_fused_w8": (C.c_int, [C.POINTER(LwmGemvW8Args), C.c_void_p]),
     "lwm_sample_tokens": (C.c_int, [C.POINTER(LwmSampleArgs), C.c_void_p]),
     "lwm_adamw_grad_norm": (C.c_int, [C.POINTER(LwmAdamWArgs), C.c_void_p]),
     "lwm_adamw_step": (C.c_int, [C.POINTER(LwmAdamWArgs), C.c_void_p]),
@@ -265,7 +280,7 @@ def bind(lib):
         fn.restype = res
         fn.argtypes = args
     for which, cls in ((0, LwmAttnArgs), (1, LwmConvArgs), (2, LwmRingArgs), (4, LwmSampleArgs), (5, LwmKv8DecodeArgs),
-                       (6, LwmKv8PrefillArgs), (7, LwmAdamWArgs), (8, LwmAdamWTensor)):
+                       (6, LwmKv8PrefillArgs), (7, LwmAdamWArgs), (8, LwmAdamWTensor), (9, LwmGemvW8Args)):
         if lib.lwm_sizeof(which) != C.sizeof(cls):
             raise ImportError(f"{cls.__name__}: ctypes mirror is {C.sizeof(cls)} bytes, library has "
                               f"{lib.lwm_sizeof(which)} (include/lwm_hip.h and lwm_amd/_capi.py out of step)")

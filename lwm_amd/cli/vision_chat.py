@@ -72,6 +72,7 @@ class Sampler:
         self.block_size = max(cfg.scan_query_chunk_size, cfg.scan_key_chunk_size) * int(self.mesh["sp"])
         self.model = C.load_checkpoint(C.build_model(cfg, True, C.torch_dtype(F.dtype, inference=True), F.seed, self.dev),
                                        F.load_checkpoint)
+        C.apply_decode_weights(self.model)          # LWM_DECODE_WEIGHTS=fp8
         self.gen = torch.Generator(device=self.dev).manual_seed(F.seed)
 
     def _read_process_vision(self, path, max_n_frames):

@@ -7,6 +7,7 @@
 #include "optim.h"
 #include "attn_decode_kv8.h"
 #include "attn_prefill_kv8.h"
+#include "gemv_w8.h"
 
 namespace lwm {
 
@@ -725,6 +726,71 @@ int lwm_gemv_bf16(const void* x, int64_t ldx, const void* w, void* y, int64_t ld
     return lwm_gemv_multi_bf16(x, ldx, 1, &w, y ? &y : nullptr, &ldy, y_f32 ? &y_f32 : nullptr, &N, workspace, rows, K, stream);
 }
 
+int lwm_w8_quantise(const void* w, void* q, float* scale, void* rounded, int32_t K, int32_t N, void* stream) {
+    using namespace lwm;
+    if (!w || !q || !scale || !rounded) return fail(LWM_EINVAL, "%s", "w8_quantise: null pointer");
+    if (K <= 0 || N <= 0) return fail(LWM_EINVAL, "%s", "w8_quantise: bad dimension");
+    if ((K & 31) || K > 8 * 12 * kGemvKT || (N % kGemvW8CPL))
+        return fail(LWM_EUNSUPPORTED, "%s: K=%ld N=%ld (need K %% 32 == 0, K <= 12288, N %% 8 == 0)", "w8_quantise", K, N);
+    if (!aligned16(w) || !aligned16(q) || !aligned16(scale) || !aligned16(rounded))
+        return fail(LWM_EINVAL, "%s", "w8_quantise: misaligned pointer");
+    W8QuantParams p;
+    p.w = (const bf16_t*)w; p.q = (uint8_t*)q; p.scale = scale; p.rounded = (bf16_t*)rounded; p.K = K; p.N = N;
+    const long grid = (long)((K + kGemvKT - 1) / kGemvKT) * ((N + kW8QuantNT - 1) / kW8QuantNT);
+    return launch("w8_quantise", w8_quantise_kernel, grid, 256, 4 * 64 * 32, stream, p);
+}
+
+int lwm_gemv_fused_w8(const LwmGemvW8Args* a, void* stream) {
+    using namespace lwm;
+    if (!a) return fail(LWM_EINVAL, "%s", "gemv_w8: args is null");
+    const int32_t nmat = a->nmat, rows = a->rows, K = a->K;
+    if (!a->x || !a->workspace) return fail(LWM_EINVAL, "%s", "gemv_w8: null pointer");
+    if (nmat < 1 || nmat > kGemvMaxMats) return fail(LWM_EINVAL, "%s", "gemv_w8: 1..3 matrices per call");
+    if (rows < 0 || K <= 0) return fail(LWM_EINVAL, "%s", "gemv_w8: bad dimension");
+    if (rows > kGemvMaxRows || (K & 31) || K > 8 * 12 * kGemvKT)
+        return fail(LWM_EUNSUPPORTED, "%s: rows=%ld K=%ld (need rows <= 4, K %% 32 == 0, K <= 12288)", "gemv_w8", rows, K);
+    if (!aligned16(a->workspace) || a->ldx < K) return fail(LWM_EINVAL, "%s", "gemv_w8: misaligned workspace or bad ldx");
+    if (a->norm_weight && (!a->ss_in || a->ss_n < 1 || a->ss_n > 64 || !(a->eps >= 0.0f)))
+        return fail(LWM_EINVAL, "%s", "gemv_w8: norm_weight needs ss_in with 1..64 partials per row and eps >= 0");
+    if (a->ss_out && (nmat != 1 || !a->y[0] || (a->N[0] % kGemvSsCols)))
+        return fail(LWM_EINVAL, "%s", "gemv_w8: ss_out needs one matrix with a bf16 output and N %% 128 == 0");
+    GemvW8Params pp;
+    memset(&pp, 0, sizeof(pp));
+    GemvParams& p = pp.g;
+    p.x = (const bf16_t*)a->x; p.part = (float*)a->workspace; p.ldx = a->ldx; p.R = rows; p.K = K; p.nmat = nmat;
+    p.KS = (K + kGemvKT - 1) / kGemvKT;
+    p.gamma = (const bf16_t*)a->norm_weight; p.ss_in = a->ss_in; p.ss_n = a->ss_n; p.eps = a->eps; p.ss_out = a->ss_out;
+    int64_t off = 0;
+    long grid = 0, quads = 0;
+    for (int i = 0; i < nmat; ++i) {
+        const int32_t n = a->N[i];
+        float* yf = a->y_f32[i];
+        void* yb = a->y[i];
+        if (!a->w[i] || !a->w_scale[i] || (!yb && !yf)) return fail(LWM_EINVAL, "%s", "gemv_w8: null matrix, null scale table or no output");
+        if (n <= 0 || (n % kGemvW8CPL)) return fail(LWM_EUNSUPPORTED, "%s: N=%ld (need N %% 8 == 0)", "gemv_w8", n);
+        if (!aligned16(a->w[i]) || !aligned16(a->w_scale[i]) || (yf && !aligned16(yf)) ||
+            (yb && ((((uintptr_t)yb) & 7) || (a->ldy[i] & 3) || a->ldy[i] < n)))
+            return fail(LWM_EINVAL, "%s", "gemv_w8: misaligned pointer or bad leading dimension");
+        if (a->residual[i] && (!yb || (((uintptr_t)a->residual[i]) & 7) || (a->ldres[i] & 3) || a->ldres[i] < n))
+            return fail(LWM_EINVAL, "%s", "gemv_w8: a residual needs a bf16 output, 8-byte alignment and ldres >= N, a multiple of 4");
+        pp.q[i] = (const uint8_t*)a->w[i]; pp.scale[i] = a->w_scale[i];
+        p.y[i] = (bf16_t*)yb; p.y_f32[i] = yf; p.ldy[i] = yb ? a->ldy[i] : 0; p.N[i] = n;
+        p.res[i] = (const bf16_t*)a->residual[i]; p.ldres[i] = a->ldres[i];
+        p.part_off[i] = off;
+        off += (int64_t)p.KS * rows * n;
+        p.blk0[i] = (int32_t)grid;
+        p.quad0[i] = (int32_t)quads;
+        grid += (long)p.KS * ((n + kGemvW8NT - 1) / kGemvW8NT);
+        quads += (long)rows * (n >> 2);
+    }
+    p.blk0[nmat] = (int32_t)grid;
+    p.quad0[nmat] = (int32_t)quads;
+    if (rows == 0) return LWM_OK;
+    int r = launch("gemv_w8", gemv_w8_kernel, grid, kGemvThreads, 3 * rows * kGemvW8NT * 4, stream, pp);
+    if (r) return r;
+    return launch("gemv_reduce", gemv_reduce_kernel, (quads * 8 + 255) / 256, 256, 64, stream, p);
+}
+
 int lwm_softmax_ce_bf16(const void* logits, const int32_t* target, const float* weight, float* nll,
                         int32_t* correct, void* dlogits, int64_t rows, int32_t V, void* stream) {
     using namespace lwm;
@@ -826,9 +892,9 @@ int lwm_adamw_step(const LwmAdamWArgs* a, void* stream) {
 int lwm_adamw_chunk(void) { return lwm::kAdamWChunk; }
 
 const char* lwm_last_error(void) { return lwm::g_err; }
-int lwm_version(void) { return 540; }
+int lwm_version(void) { return 550; }
 int lwm_sizeof(int which) {
-    return which == 0 ? (int)sizeof(LwmAttnArgs) : which == 1 ? (int)sizeof(LwmConvArgs) : which == 2 ? (int)sizeof(LwmRingArgs) : which == 3 ? (int)sizeof(LwmGemvArgs) : which == 4 ? (int)sizeof(LwmSampleArgs) : which == 5 ? (int)sizeof(LwmKv8DecodeArgs) : which == 6 ? (int)sizeof(LwmKv8PrefillArgs) : which == 7 ? (int)sizeof(LwmAdamWArgs) : which == 8 ? (int)sizeof(LwmAdamWTensor) : -1;
+    return which == 0 ? (int)sizeof(LwmAttnArgs) : which == 1 ? (int)sizeof(LwmConvArgs) : which == 2 ? (int)sizeof(LwmRingArgs) : which == 3 ? (int)sizeof(LwmGemvArgs) : which == 4 ? (int)sizeof(LwmSampleArgs) : which == 5 ? (int)sizeof(LwmKv8DecodeArgs) : which == 6 ? (int)sizeof(LwmKv8PrefillArgs) : which == 7 ? (int)sizeof(LwmAdamWArgs) : which == 8 ? (int)sizeof(LwmAdamWTensor) : which == 9 ? (int)sizeof(LwmGemvW8Args) : -1;
 }
 
 }  // extern "C"

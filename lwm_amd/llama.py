@@ -373,6 +373,7 @@ class LLaMAForCausalLM(torch.nn.Module):
         self.ln_f = RMSNorm(cfg.hidden_size, cfg.rms_norm_eps, dtype)
         self.lm_head = _dense(cfg.hidden_size, cfg.vocab_size, cfg.initializer_range, dtype)
         self._freqs = None
+        self._w8 = None            # quantize_decode_weights("fp8"): {parameter name: lwm_amd.w8.W8Kernel}
 
     def _table(self, device):
         if self._freqs is None or self._freqs.device != device:
@@ -437,11 +438,63 @@ class LLaMAForCausalLM(torch.nn.Module):
             norm._lwm_bf16 = hit
         return hit[1]
 
+    # ---- 8-bit decode weights (extension; include/lwm_hip.h "8-bit decode weights", lwm_amd/w8.py)
+    def _decode_weight_params(self):
+        """(name, parameter) of every kernel a cached one-token step streams through the GEMV"""
+        for i, blk in enumerate(self.h):
+            for mod, names in (("attention", ("wq", "wk", "wv", "wo")), ("feed_forward", ("w1", "w2", "w3"))):
+                for n in names:
+                    yield f"h.{i}.{mod}.{n}", getattr(getattr(blk, mod), n)
+        yield "lm_head", self.lm_head
+
+    @torch.no_grad()
+    def quantize_decode_weights(self, mode="fp8"):
+        """mode="fp8": every projection kernel of the blocks and lm_head is ROUNDED IN PLACE to its e4m3-representable
+        values (per 128 rows of K and column one power-of-two scale) and an 8-bit pack of it is kept beside it.  After it
+        the model IS the rounded model: prefill, training ops, LWM_DECODE_FUSED=0, batches over 4 rows run as before on the
+        rounded bf16 parameters, while the fused one-token step and the <= 4-row f32 logits of the heads stream the packs
+        (lwm_gemv_fused_w8) -- bit for bit what the bf16 GEMV gives on the rounded parameters, from 0.516 of the bytes.
+        The bf16 parameters stay: the weights take 1.516x their memory.  A pack whose parameter changes afterwards is
+        refused at its next use (RuntimeError): quantise again.  mode="bf16" / None = drop_decode_weights().
+        bf16 models on one rank."""
+        if mode in (None, "bf16"):
+            return self.drop_decode_weights()
+        if mode != "fp8":
+            raise ValueError(f"quantize_decode_weights({mode!r}): 'fp8', or 'bf16' / None (drop_decode_weights)")
+        if self.dtype != torch.bfloat16:
+            raise NotImplementedError("quantize_decode_weights('fp8') with a float32 model: the 8-bit packs are made from bf16 "
+                                      "kernels and the GEMV that streams them takes bf16 activations (--dtype=bf16, or bf16 weights)")
+        if sp_size_rank("sp")[0] > 1:
+            raise NotImplementedError("quantize_decode_weights('fp8') with sp > 1: the fused one-token step runs on one rank "
+                                      "(one rank, or bf16 decode weights)")
+        from .w8 import quantise_weight
+        packs = {}
+        for name, p in self._decode_weight_params():
+            try:
+                packs[name] = quantise_weight(p)
+            except ValueError as e:
+                raise ValueError(f"quantize_decode_weights('fp8'): {name}: {e}") from None
+        self._w8 = packs
+        return self
+
+    def drop_decode_weights(self):
+        """Back to bf16 weight streaming.  The parameters stay as they are (rounded, if they were quantised)."""
+        self._w8 = None
+        return self
+
+    def _w8_packs(self, names, kernels):
+        """the packs of `kernels`, each checked against its parameter as it is NOW"""
+        return [self._w8[n].check(k, n) for n, k in zip(names, kernels)]
+
     def _decode_layers_fused(self, x, fc, attention_mask, position_ids, cache):
         """The blocks of a cached one-token step (lwm/llama.py:704-744 with q_len = 1) with each RMSNorm folded into the
         x load of the projections that follow it and each residual add into the reduction of the projection before it:
         per layer 4 fewer launches of the ~19; same roundings as the separate kernels (rstd sums in another order)."""
         from .llama_ops import gemv_fused
+        if getattr(self, "_w8", None) is not None:         # the same launch pairs over the 8-bit packs (bit for bit on the rounded parameters)
+            from .w8 import gemv_fused_w8
+            names = {id(p): n for n, p in self._decode_weight_params()}
+            gemv_fused = lambda x, ks, **kw: gemv_fused_w8(x, self._w8_packs([names[id(k)] for k in ks], ks), **kw)    # noqa: E731
         B, _, d = x.shape
         H, D = self.cfg.num_attention_heads, d // self.cfg.num_attention_heads
         x2 = x.reshape(B, d)
@@ -559,7 +612,7 @@ class LLaMAForCausalLM(torch.nn.Module):
             step_in, pos = input_ids[:, a:], pos[:, a:].contiguous()
         for _ in range(n_eager):
             h = self.hidden_states(step_in, ext, None, pos, cache)
-            step_in = emit(dense(h[:, -1], head, torch.float32))
+            step_in = emit(_head_logits(self, h[:, -1], head))
             pos = (pos[:, -1:] + 1).contiguous()
         if graph and max_new_tokens > 1:
             import torch.distributed as dist
@@ -574,7 +627,7 @@ class LLaMAForCausalLM(torch.nn.Module):
                 mask = ((ar[None, :] <= idx) & (ext > 0))[:, None, None, :]
                 for c in dcache:
                     c["mask_dev"] = mask
-                logits = dense(self.hidden_states(tok, ext, None, posd, dcache)[:, -1], head, torch.float32)
+                logits = _head_logits(self, self.hidden_states(tok, ext, None, posd, dcache)[:, -1], head)
                 tok.copy_(logits.argmax(-1, keepdim=True).to(tok.dtype))
                 posd.add_(1)
                 idx.add_(1)
@@ -597,6 +650,29 @@ class LLaMAForCausalLM(torch.nn.Module):
         scoring of a short batch on every rank): no collective, each rank gets the whole loss."""
         h = self.hidden_states(input_tokens, attention_mask, segment_ids, position_ids, layout=layout)
         return chunked_lm_head_loss(h, self.lm_head, target_tokens, loss_masks, chunk, sp_sharded=sp_sharded)
+
+
+def w8_head_logits(model, h, head):
+    """f32 logits of a head through its 8-bit pack (quantize_decode_weights), where the model has one for `head` and the
+    rows go through the GEMV (at most four, no autograd); None otherwise -- the caller then runs
+    `dense(h, head, torch.float32)` as before (a stand-in model without packs always gets None)"""
+    packs = getattr(model, "_w8", None)
+    if packs is None:
+        return None
+    same = lambda p: p is head or (p.data_ptr() == head.data_ptr() and p.shape == head.shape and p.stride() == head.stride())
+    name = next((n for n in packs if "." not in n and same(getattr(model, n))), None)
+    rows = h.numel() // h.shape[-1]
+    if name is None or rows > 4 or not h.is_cuda or h.dtype != torch.bfloat16 or torch.is_grad_enabled():
+        return None
+    from .w8 import gemv_fused_w8
+    (y,) = gemv_fused_w8(h.reshape(rows, h.shape[-1]), model._w8_packs((name,), (head,)), out_dtype=torch.float32)
+    return y.reshape(*h.shape[:-1], y.shape[-1])
+
+
+def _head_logits(model, h, head):
+    y = w8_head_logits(model, h, head)
+    return dense(h, head, torch.float32) if y is None else y
+
 
 def check_prefill_chunk(prefill_chunk):
     """generate(prefill_chunk=): None, or a block length >= 1 on one rank"""

@@ -9,7 +9,8 @@ from __future__ import annotations
 import torch
 
 from . import ops as _ops
-from .llama import LLaMAConfig, LLaMAForCausalLM, _dense, cache_kwargs, capture_decode_step, check_prefill_chunk
+from .llama import (LLaMAConfig, LLaMAForCausalLM, _dense, cache_kwargs, capture_decode_step, check_prefill_chunk,
+                    w8_head_logits)
 from .llama_ops import chunked_lm_head_loss, dense
 from .ringattention import sp_size_rank
 
@@ -22,6 +23,12 @@ class VideoLLaMAConfig(LLaMAConfig):
         self.vision_vocab_size = vision_vocab_size      # 8192 + 256
         self.tie_vision_embeddings = tie_vision_embeddings
         self.sample_mode = sample_mode
+
+
+def _head_logits(model, h, head):
+    """`dense(h, head, torch.float32)`, through the head's 8-bit pack where the model has one (llama.w8_head_logits)"""
+    y = w8_head_logits(model, h, head)
+    return dense(h, head, torch.float32) if y is None else y
 
 
 class VideoLLaMAForCausalLM(LLaMAForCausalLM):
@@ -54,6 +61,13 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
         for i, blk in enumerate(self.h):
             x = blk(x, fc, attention_mask, segment_ids, position_ids, None if cache is None else cache[i], layout)
         return self.ln_f(x)
+
+    def _decode_weight_params(self):
+        """... and the vision head where it is a parameter of its own (the tied head is a transposed view of vte and
+        stays on the bf16 path)"""
+        yield from super()._decode_weight_params()
+        if not self.cfg.tie_vision_embeddings and self.vision_head.is_contiguous():
+            yield "vision_head", self.vision_head
 
     def _vision_kernel(self):
         return self.vte.t() if self.cfg.tie_vision_embeddings else self.vision_head
@@ -157,7 +171,7 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
         every = self.DONE_CHECK_EVERY
         all_done = lambda i: done is not None and (i + 1) % every == 0 and bool(done.all())    # after token i
 
-        logits = dense(h, head, torch.float32)
+        logits = _head_logits(self, h, head)
         keep(logits)
         _ops.sample_tokens(logits, step=0, **kw)
         if not graph:
@@ -165,7 +179,7 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
                 if all_done(i - 1):
                     break
                 h, pos = self._step(tok, cache, ext, pos)
-                logits = dense(h, head, torch.float32)
+                logits = _head_logits(self, h, head)
                 keep(logits)
                 _ops.sample_tokens(logits, step=i, **kw)
         elif max_new_tokens > 1 and not all_done(0):
@@ -179,7 +193,7 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
                 mask = ((ar[None, :] <= idx) & (ext > 0))[:, None, None, :]
                 for c in dcache:
                     c["mask_dev"] = mask
-                lg = dense(self.hidden_states(tok, None, ext, None, posd, dcache)[:, -1], head, torch.float32)
+                lg = _head_logits(self, self.hidden_states(tok, None, ext, None, posd, dcache)[:, -1], head)
                 _ops.sample_tokens(lg, step_dev=idx, step_base=index - 1, **kw)
                 posd.add_(1)
                 idx.add_(1)
@@ -228,7 +242,7 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
         done = torch.zeros(B, dtype=torch.bool, device=input_ids.device)
         logits_out = []
         for i in range(max_new_tokens):
-            logits = dense(h, head, torch.float32)
+            logits = _head_logits(self, h, head)
             if return_logits:
                 logits_out.append(logits.clone())
             tok = self._pick(logits, temperature, top_k, do_sample, generator).to(input_ids.dtype)
@@ -278,7 +292,7 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
         out = torch.empty((B, max_new_tokens), dtype=input_ids.dtype, device=input_ids.device)
         logits_out = []
         for i in range(max_new_tokens):
-            logits = dense(h, head, torch.float32)
+            logits = _head_logits(self, h, head)
             if return_logits:
                 logits_out.append(logits.clone())
             cond, uncond = logits[:B], logits[B:]
