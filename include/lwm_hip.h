@@ -555,6 +555,34 @@ typedef struct LwmGemvW8Args {
 } LwmGemvW8Args;
 int lwm_gemv_fused_w8(const LwmGemvW8Args* args, void* stream);
 
+/* ------------------------------------------------------------------ decode projections for 1..32 rows (lwm_version() >= 560)
+ * The same products on the matrix pipe (v_mfma_f32_16x16x32_bf16) for batches past the GEMV's four rows: W is still read
+ * once.  Every field of LwmGemvArgs / LwmGemvW8Args means what it means for lwm_gemv_fused_bf16 / lwm_gemv_fused_w8, with
+ *   1 <= rows <= 32 (rows == 0 is refused); K % 32 == 0, K <= 12288; N[i] % 8 == 0; 1..3 matrices that share x;
+ *   x 16-byte aligned with ldx % 8 == 0 and norm_weight 16-byte aligned (both are read 16 bytes at a time);
+ *   residual and ss_out with ONE matrix only;
+ *   workspace of the sum of lwm_gemm_rows_workspace_bytes(rows, K, N[i]) bytes, 16-byte aligned.
+ * Refusals return LWM_EINVAL / LWM_EUNSUPPORTED, leave a message in lwm_last_error() and write nothing.
+ * Summation contract: K is cut into groups of 128 rows (the GEMV's partition, = the scale groups of the 8-bit format); the
+ *   workspace receives one f32 partial per group, [ceil(K/128)][rows][N[i]] per matrix, each accumulated in f32 by the
+ *   matrix instruction over exact bf16 x bf16 products, and the partials of an output are added along the GEMV's fixed
+ *   tree by the GEMV's reduction (residual add bf16(bf16(x . W) + residual), ss_out, bf16 / f32 stores: the same code).  No
+ *   atomics: the same input gives the same bits.  Within a group the order of the sum is the instruction's, so results
+ *   agree with lwm_gemv_fused_bf16 to f32 rounding (|y_f32 - exact| <= K 2^-23 sum_k |x_k W_kn|), and bit for bit wherever
+ *   every partial sum is exact (small integers).  RMSNorm on load feeds the instruction bit for bit the normalised x the
+ *   GEMV feeds its FMAs (the same expression, the same tree over ss_in).
+ * Exactness domain of the 8-bit entry: as for lwm_gemv_fused_w8 -- e4m3(q) * s is a bf16 value whenever it is a normal
+ *   number, and with power-of-two scales and neither overflow nor underflow in the partial sums (scales between 2^-40 and
+ *   2^40 and activations of ordinary size are well inside) outputs and workspace partials are BIT FOR BIT those of
+ *   lwm_gemm_rows_fused_bf16 on the `rounded` weights: the bytes become bf16 before the instruction sees them and the
+ *   scale multiplies each partial once.
+ * Row independence: the bits of output row r depend on x[r], the weights and the fused operands of row r only -- not on
+ *   `rows`, not on the row's position in the call, not on what the other rows hold.  A prompt decodes to the same logits
+ *   in a batch of 5 as in a batch of 32. */
+int64_t lwm_gemm_rows_workspace_bytes(int32_t rows, int32_t K, int32_t N);
+int lwm_gemm_rows_fused_bf16(const LwmGemvArgs* args, void* stream);     /* rows 1..32 */
+int lwm_gemm_rows_fused_w8(const LwmGemvW8Args* args, void* stream);
+
 /* tux.cross_entropy_loss_and_accuracy as used at lwm/train.py:177-181, :192-201, per row of
  * bf16 logits [rows, V] (V % 8 == 0, V <= 32768): nll[r] = logsumexp(row) - row[target[r]] in
  * f32; correct[r] = (first argmax == target[r]) (may be NULL); and, if dlogits != NULL, the

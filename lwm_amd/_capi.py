@@ -253,6 +253,9 @@ PROTOTYPES = {
     "lwm_gemv_fused_bf16": (C.c_int, [C.POINTER(LwmGemvArgs), C.c_void_p]),
     "lwm_w8_quantise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "lwm_gemv_fused_w8": (C.c_int, [C.POINTER(LwmGemvW8Args), C.c_void_p]),
+    "lwm_gemm_rows_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "lwm_gemm_rows_fused_bf16": (C.c_int, [C.POINTER(LwmGemvArgs), C.c_void_p]),
+    "lwm_gemm_rows_fused_w8": (C.c_int, [C.POINTER(LwmGemvW8Args), C.c_void_p]),
     "lwm_sample_tokens": (C.c_int, [C.POINTER(LwmSampleArgs), C.c_void_p]),
     "lwm_adamw_grad_norm": (C.c_int, [C.POINTER(LwmAdamWArgs), C.c_void_p]),
     "lwm_adamw_step": (C.c_int, [C.POINTER(LwmAdamWArgs), C.c_void_p]),

@@ -62,6 +62,14 @@ def apply_decode_weights(model):
     if mode == "fp8":
         model.quantize_decode_weights("fp8")
         note("LWM_DECODE_WEIGHTS=fp8: projection kernels rounded in place to e4m3 values; one-token steps stream the 8-bit packs")
+    # LWM_DECODE_ROWS=N is read by the model itself (model.decode_rows) at every step: a bad value ends the run here, by name
+    from ..llama_ops import parse_decode_rows
+    try:
+        rows = parse_decode_rows(os.environ.get("LWM_DECODE_ROWS"))
+    except ValueError as e:
+        raise SystemExit(str(e)) from None
+    if rows:
+        note(f"LWM_DECODE_ROWS={rows}: one-token steps of up to {rows} batch rows run through the fused step (lwm_gemm_rows_fused_*)")
     return model
 
 

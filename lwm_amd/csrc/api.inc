@@ -8,6 +8,7 @@
 #include "attn_decode_kv8.h"
 #include "attn_prefill_kv8.h"
 #include "gemv_w8.h"
+#include "gemm_rows.h"
 
 namespace lwm {
 
@@ -791,6 +792,76 @@ int lwm_gemv_fused_w8(const LwmGemvW8Args* a, void* stream) {
     return launch("gemv_reduce", gemv_reduce_kernel, (quads * 8 + 255) / 256, 256, 64, stream, p);
 }
 
+// ------------------------------------------------------------------ 1..32 rows on the matrix pipe (gemm_rows.h)
+}  // extern "C"
+namespace lwm {
+// the checks and the launch pair of both entries: A = LwmGemvArgs (scales null) or LwmGemvW8Args
+template <class A>
+static int gemm_rows_run(const A* a, const float* const* w_scale, const char* who, void* stream) {
+    const bool w8 = w_scale != nullptr;
+    if (!a) return fail(LWM_EINVAL, "%s: args is null", who);
+    const int32_t nmat = a->nmat, rows = a->rows, K = a->K;
+    if (!a->x || !a->workspace) return fail(LWM_EINVAL, "%s: null pointer", who);
+    if (nmat < 1 || nmat > kGemvMaxMats) return fail(LWM_EINVAL, "%s: 1..3 matrices per call", who);
+    if (rows < 0 || K <= 0) return fail(LWM_EINVAL, "%s: bad dimension", who);
+    if (rows < 1 || rows > kRowsMax || (K & 31) || K > 8 * 12 * kGemvKT)
+        return fail(LWM_EUNSUPPORTED, "%s: rows=%ld K=%ld (need 1 <= rows <= 32, K %% 32 == 0, K <= 12288)", who, rows, K);
+    if (!aligned16(a->workspace) || !aligned16(a->x) || a->ldx < K || (a->ldx & 7))
+        return fail(LWM_EINVAL, "%s: misaligned workspace or x, or bad ldx (need ldx >= K, ldx %% 8 == 0)", who);
+    if (a->norm_weight && (!aligned16(a->norm_weight) || !a->ss_in || a->ss_n < 1 || a->ss_n > 64 || !(a->eps >= 0.0f)))
+        return fail(LWM_EINVAL, "%s: norm_weight needs 16-byte alignment, ss_in with 1..64 partials per row and eps >= 0", who);
+    if (a->ss_out && (nmat != 1 || !a->y[0] || (a->N[0] % kGemvSsCols)))
+        return fail(LWM_EINVAL, "%s: ss_out needs one matrix with a bf16 output and N %% 128 == 0", who);
+    GemvW8Params pp;
+    memset(&pp, 0, sizeof(pp));
+    GemvParams& p = pp.g;
+    p.x = (const bf16_t*)a->x; p.part = (float*)a->workspace; p.ldx = a->ldx; p.R = rows; p.K = K; p.nmat = nmat;
+    p.KS = (K + kGemvKT - 1) / kGemvKT;
+    p.gamma = (const bf16_t*)a->norm_weight; p.ss_in = a->ss_in; p.ss_n = a->ss_n; p.eps = a->eps; p.ss_out = a->ss_out;
+    int64_t off = 0;
+    long grid = 0, quads = 0;
+    for (int i = 0; i < nmat; ++i) {
+        const int32_t n = a->N[i];
+        float* yf = a->y_f32[i];
+        void* yb = a->y[i];
+        if (!a->w[i] || (w8 && !w_scale[i]) || (!yb && !yf)) return fail(LWM_EINVAL, "%s: null matrix, null scale table or no output", who);
+        if (n <= 0 || (n & 7)) return fail(LWM_EUNSUPPORTED, "%s: N=%ld (need N %% 8 == 0)", who, n);
+        if (!aligned16(a->w[i]) || (w8 && !aligned16(w_scale[i])) || (yf && !aligned16(yf)) ||
+            (yb && ((((uintptr_t)yb) & 7) || (a->ldy[i] & 3) || a->ldy[i] < n)))
+            return fail(LWM_EINVAL, "%s: misaligned pointer or bad leading dimension", who);
+        if (a->residual[i] && (nmat != 1 || !yb || (((uintptr_t)a->residual[i]) & 7) || (a->ldres[i] & 3) || a->ldres[i] < n))
+            return fail(LWM_EINVAL, "%s: a residual needs one matrix with a bf16 output, 8-byte alignment and ldres >= N, a multiple of 4", who);
+        if (w8) { pp.q[i] = (const uint8_t*)a->w[i]; pp.scale[i] = w_scale[i]; }
+        else p.w[i] = (const bf16_t*)a->w[i];
+        p.y[i] = (bf16_t*)yb; p.y_f32[i] = yf; p.ldy[i] = yb ? a->ldy[i] : 0; p.N[i] = n;
+        p.res[i] = (const bf16_t*)a->residual[i]; p.ldres[i] = a->ldres[i];
+        p.part_off[i] = off;
+        off += (int64_t)p.KS * rows * n;
+        p.blk0[i] = (int32_t)grid;
+        p.quad0[i] = (int32_t)quads;
+        grid += (long)p.KS * ((n + kRowsNT - 1) / kRowsNT);
+        quads += (long)rows * (n >> 2);
+    }
+    p.blk0[nmat] = (int32_t)grid;
+    p.quad0[nmat] = (int32_t)quads;
+    int r = w8 ? launch("gemm_rows_w8", gemm_rows_w8_kernel, grid, kRowsThreads, kRowsLdsBytes, stream, pp)
+               : launch("gemm_rows_bf16", gemm_rows_bf16_kernel, grid, kRowsThreads, kRowsLdsBytes, stream, p);
+    if (r) return r;
+    return launch("gemv_reduce", gemv_reduce_kernel, (quads * 8 + 255) / 256, 256, 64, stream, p);
+}
+}  // namespace lwm
+extern "C" {
+
+int64_t lwm_gemm_rows_workspace_bytes(int32_t rows, int32_t K, int32_t N) { return lwm_gemv_workspace_bytes(rows, K, N); }
+
+int lwm_gemm_rows_fused_bf16(const LwmGemvArgs* a, void* stream) {
+    return lwm::gemm_rows_run(a, (const float* const*)nullptr, "gemm_rows", stream);
+}
+
+int lwm_gemm_rows_fused_w8(const LwmGemvW8Args* a, void* stream) {
+    return lwm::gemm_rows_run(a, a ? a->w_scale : (const float* const*)nullptr, "gemm_rows_w8", stream);
+}
+
 int lwm_softmax_ce_bf16(const void* logits, const int32_t* target, const float* weight, float* nll,
                         int32_t* correct, void* dlogits, int64_t rows, int32_t V, void* stream) {
     using namespace lwm;
@@ -892,7 +963,7 @@ int lwm_adamw_step(const LwmAdamWArgs* a, void* stream) {
 int lwm_adamw_chunk(void) { return lwm::kAdamWChunk; }
 
 const char* lwm_last_error(void) { return lwm::g_err; }
-int lwm_version(void) { return 550; }
+int lwm_version(void) { return 560; }
 int lwm_sizeof(int which) {
     return which == 0 ? (int)sizeof(LwmAttnArgs) : which == 1 ? (int)sizeof(LwmConvArgs) : which == 2 ? (int)sizeof(LwmRingArgs) : which == 3 ? (int)sizeof(LwmGemvArgs) : which == 4 ? (int)sizeof(LwmSampleArgs) : which == 5 ? (int)sizeof(LwmKv8DecodeArgs) : which == 6 ? (int)sizeof(LwmKv8PrefillArgs) : which == 7 ? (int)sizeof(LwmAdamWArgs) : which == 8 ? (int)sizeof(LwmAdamWTensor) : which == 9 ? (int)sizeof(LwmGemvW8Args) : -1;
 }

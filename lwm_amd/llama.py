@@ -17,8 +17,9 @@ import os
 import torch
 
 from . import ops as _ops
-from .llama_ops import (LLaMAMLP, RMSNorm, apply_rotary_emb, chunked_lm_head_loss, dense, dense_fused, dense_multi,
-                        fused_dense_ok, precompute_freqs_cis, qkv_rope, rmsnorm_residual, swiglu)
+from .llama_ops import (LLaMAMLP, RMSNorm, apply_rotary_emb, chunked_lm_head_loss, decode_rows_scope, dense, dense_fused,
+                        dense_multi, fused_dense_ok, parse_decode_rows, precompute_freqs_cis, qkv_rope, rmsnorm_residual,
+                        rows_x_ok, swiglu)
 from .ringattention import (blockwise_feedforward, concatenate_to_cache, ringattention,
                             ringattention_inference, sp_layout_is_explicit, sp_positions, sp_size_rank)
 
@@ -374,6 +375,7 @@ class LLaMAForCausalLM(torch.nn.Module):
         self.lm_head = _dense(cfg.hidden_size, cfg.vocab_size, cfg.initializer_range, dtype)
         self._freqs = None
         self._w8 = None            # quantize_decode_weights("fp8"): {parameter name: lwm_amd.w8.W8Kernel}
+        self._decode_rows = None   # decode_rows: None = LWM_DECODE_ROWS
 
     def _table(self, device):
         if self._freqs is None or self._freqs.device != device:
@@ -407,23 +409,41 @@ class LLaMAForCausalLM(torch.nn.Module):
             raise ValueError("cached inference over a sequence ring needs explicit global position_ids")
         return n_sp, position_ids
 
+    @property
+    def decode_rows(self):
+        """None, or N in 5..32: cached one-token steps of up to N batch rows run through the fused step and
+        lwm_gemm_rows_fused_bf16 / _w8 (csrc/gemm_rows.h) instead of block by block through the library GEMMs, and the
+        heads' f32 logits with them.  Opt-in (such steps then differ in their low bits); unset, the attribute reads
+        LWM_DECODE_ROWS.  Values outside 5..32 raise ValueError."""
+        return parse_decode_rows(os.environ.get("LWM_DECODE_ROWS")) if self._decode_rows is None else self._decode_rows
+
+    @decode_rows.setter
+    def decode_rows(self, n):
+        self._decode_rows = parse_decode_rows(n, "decode_rows")
+
     def hidden_states(self, input_ids, attention_mask=None, segment_ids=None, position_ids=None, cache=None, layout=None):
         n_sp, position_ids = self._ring_position_ids(input_ids, position_ids, cache, layout)
         x = torch.nn.functional.embedding(input_ids.long(), self.wte)
+        return self._layers(x, n_sp, attention_mask, segment_ids, position_ids, cache, layout)
+
+    def _layers(self, x, n_sp, attention_mask, segment_ids, position_ids, cache, layout):
+        """the blocks and the final norm over embedded tokens x (B, S, d)"""
         fc = self._table(x.device)
         if cache is not None and self._fused_decode_ok(x, n_sp):
             return self.ln_f(self._decode_layers_fused(x, fc, attention_mask, position_ids, cache))
-        for i, blk in enumerate(self.h):
-            x = blk(x, fc, attention_mask, segment_ids, position_ids, None if cache is None else cache[i], layout)
+        with decode_rows_scope(self.decode_rows):
+            for i, blk in enumerate(self.h):
+                x = blk(x, fc, attention_mask, segment_ids, position_ids, None if cache is None else cache[i], layout)
         return self.ln_f(x)
 
     def _fused_decode_ok(self, x, n_sp):
         """One token per batch row through the KV cache, bf16, no autograd, one rank: the layers can run as GEMV launch
-        pairs that carry their neighbours (lwm_gemv_fused_bf16; LWM_DECODE_FUSED=0 issues every launch on its own)."""
+        pairs that carry their neighbours (lwm_gemv_fused_bf16; LWM_DECODE_FUSED=0 issues every launch on its own).  At most
+        four rows -- or decode_rows of them, where that is set: rows 5.. then go through lwm_gemm_rows_fused_*."""
         d = self.cfg.hidden_size
         # (d / 128 partial sums of squares per row ride along: lwm_gemv_fused_bf16 takes at most 64 of them; the weights
         # must be what the GEMV streams -- contiguous bf16 -- or the per-block path runs)
-        return (os.environ.get("LWM_DECODE_FUSED", "1") == "1" and x.shape[1] == 1 and x.shape[0] <= 4 and n_sp == 1
+        return (os.environ.get("LWM_DECODE_FUSED", "1") == "1" and x.shape[1] == 1 and x.shape[0] <= (self.decode_rows or 4) and n_sp == 1
                 and x.is_cuda and x.dtype == torch.bfloat16 and not torch.is_grad_enabled() and d % 128 == 0
                 and d <= 8192 and self.cfg.intermediate_size % 32 == 0 and self.cfg.intermediate_size <= 12288
                 and all(p.dtype == torch.bfloat16 and p.is_contiguous() for p in self.h[0].parameters() if p.dim() == 2))
@@ -451,9 +471,9 @@ class LLaMAForCausalLM(torch.nn.Module):
     def quantize_decode_weights(self, mode="fp8"):
         """mode="fp8": every projection kernel of the blocks and lm_head is ROUNDED IN PLACE to its e4m3-representable
         values (per 128 rows of K and column one power-of-two scale) and an 8-bit pack of it is kept beside it.  After it
-        the model IS the rounded model: prefill, training ops, LWM_DECODE_FUSED=0, batches over 4 rows run as before on the
-        rounded bf16 parameters, while the fused one-token step and the <= 4-row f32 logits of the heads stream the packs
-        (lwm_gemv_fused_w8) -- bit for bit what the bf16 GEMV gives on the rounded parameters, from 0.516 of the bytes.
+        the model IS the rounded model: prefill, training ops, LWM_DECODE_FUSED=0, batches over 4 rows (over decode_rows, where
+        that is set) run as before on the rounded bf16 parameters, while the fused one-token step and the f32 logits of the
+        heads at those row counts stream the packs (lwm_gemv_fused_w8; lwm_gemm_rows_fused_w8 above 4 rows) -- bit for bit what the bf16 GEMV gives on the rounded parameters, from 0.516 of the bytes.
         The bf16 parameters stay: the weights take 1.516x their memory.  A pack whose parameter changes afterwards is
         refused at its next use (RuntimeError): quantise again.  mode="bf16" / None = drop_decode_weights().
         bf16 models on one rank."""
@@ -490,12 +510,15 @@ class LLaMAForCausalLM(torch.nn.Module):
         """The blocks of a cached one-token step (lwm/llama.py:704-744 with q_len = 1) with each RMSNorm folded into the
         x load of the projections that follow it and each residual add into the reduction of the projection before it:
         per layer 4 fewer launches of the ~19; same roundings as the separate kernels (rstd sums in another order)."""
-        from .llama_ops import gemv_fused
-        if getattr(self, "_w8", None) is not None:         # the same launch pairs over the 8-bit packs (bit for bit on the rounded parameters)
-            from .w8 import gemv_fused_w8
-            names = {id(p): n for n, p in self._decode_weight_params()}
-            gemv_fused = lambda x, ks, **kw: gemv_fused_w8(x, self._w8_packs([names[id(k)] for k in ks], ks), **kw)    # noqa: E731
+        from . import llama_ops, w8
         B, _, d = x.shape
+        # <= 4 rows: the GEMV; above (decode_rows): the same launch pairs on the matrix pipe.  (Looked up at call time: both
+        # modules' entries can be wrapped.)
+        gemv_fused = llama_ops.gemv_fused if B <= 4 else llama_ops.gemm_rows_fused
+        if getattr(self, "_w8", None) is not None:         # the same launch pairs over the 8-bit packs (bit for bit on the rounded parameters)
+            fused_w8 = w8.gemv_fused_w8 if B <= 4 else w8.gemm_rows_fused_w8
+            names = {id(p): n for n, p in self._decode_weight_params()}
+            gemv_fused = lambda x, ks, **kw: fused_w8(x, self._w8_packs([names[id(k)] for k in ks], ks), **kw)    # noqa: E731
         H, D = self.cfg.num_attention_heads, d // self.cfg.num_attention_heads
         x2 = x.reshape(B, d)
         ss = torch.zeros(B, 32, dtype=torch.float32, device=x.device)
@@ -662,16 +685,37 @@ def w8_head_logits(model, h, head):
     same = lambda p: p is head or (p.data_ptr() == head.data_ptr() and p.shape == head.shape and p.stride() == head.stride())
     name = next((n for n in packs if "." not in n and same(getattr(model, n))), None)
     rows = h.numel() // h.shape[-1]
-    if name is None or rows > 4 or not h.is_cuda or h.dtype != torch.bfloat16 or torch.is_grad_enabled():
+    limit = max(4, model_decode_rows(model) or 4)
+    if name is None or rows > limit or not h.is_cuda or h.dtype != torch.bfloat16 or torch.is_grad_enabled():
         return None
-    from .w8 import gemv_fused_w8
-    (y,) = gemv_fused_w8(h.reshape(rows, h.shape[-1]), model._w8_packs((name,), (head,)), out_dtype=torch.float32)
+    from . import w8
+    h2 = h.reshape(rows, h.shape[-1])
+    if rows > 4 and not rows_x_ok(h2):
+        h2 = h2.clone(memory_format=torch.contiguous_format)
+    fused = w8.gemv_fused_w8 if rows <= 4 else w8.gemm_rows_fused_w8
+    (y,) = fused(h2, model._w8_packs((name,), (head,)), out_dtype=torch.float32)
     return y.reshape(*h.shape[:-1], y.shape[-1])
 
 
-def _head_logits(model, h, head):
+def model_decode_rows(model):
+    """model.decode_rows; LWM_DECODE_ROWS for a stand-in model without the attribute"""
+    try:
+        return model.decode_rows
+    except AttributeError:
+        return parse_decode_rows(os.environ.get("LWM_DECODE_ROWS"))
+
+
+def head_logits(model, h, head):
+    """f32 logits of `head`: through its 8-bit pack where the model has one, else `dense(h, head, torch.float32)` (the GEMV
+    for <= 4 rows, lwm_gemm_rows_fused_bf16 up to model.decode_rows, the library beyond)"""
     y = w8_head_logits(model, h, head)
-    return dense(h, head, torch.float32) if y is None else y
+    if y is not None:
+        return y
+    with decode_rows_scope(model_decode_rows(model)):
+        return dense(h, head, torch.float32)
+
+
+_head_logits = head_logits
 
 
 def check_prefill_chunk(prefill_chunk):

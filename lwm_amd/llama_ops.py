@@ -19,6 +19,7 @@ import torch
 
 from . import _capi
 from ._lib import lib
+from .decode_rows import decode_rows_limit, decode_rows_scope, gemm_rows_fused, parse_decode_rows, rows_x_ok  # noqa: F401
 from .ops import _stream_ptr, _t4
 
 _DTYPES = (torch.bfloat16, torch.float32)
@@ -395,14 +396,23 @@ def gemv_fused(x, kernels, *, norm=None, residual=None, want_ss=False, out_dtype
     norm = (ss (rows, n <= 64) f32 partial sums of squares of x's rows, weight (K,) bf16, eps): RMSNorm on load;
     residual (rows, N) bf16 (one kernel): y = bf16(bf16(x @ W) + residual); want_ss: also return the (rows, N / 128)
     partial sums of squares of y for the next norm.  -> [y_i] or ([y_i], ss)."""
+    return _fused_call(False, x, kernels, norm, residual, want_ss, out_dtype)
+
+
+def _fused_call(rows_entry, x, kernels, norm, residual, want_ss, out_dtype):
     rows, K = _gemv_check(x, kernels, out_dtype)
     L = lib()
     n = len(kernels)
     Ns = [int(k.shape[1]) for k in kernels]
-    key = (x.device, rows, K, tuple(Ns))
+    if rows_entry:
+        if not 1 <= rows <= 32:
+            raise ValueError(f"gemm_rows_fused: {rows} rows (1..32)")
+        if not rows_x_ok(x):
+            raise ValueError("gemm_rows_fused: x must be 16-byte aligned with a row stride that is a multiple of 8 elements")
+    key = (x.device, rows, K, tuple(Ns)) + (("rows",) if rows_entry else ())
     ws = _GEMV_WS.get(key)
-    if ws is None:
-        need = sum(L.lwm_gemv_workspace_bytes(rows, K, N) for N in Ns)
+    if ws is None:                     # (one workspace per shape: a hipGraph replays with the pointers it captured)
+        need = sum((L.lwm_gemm_rows_workspace_bytes if rows_entry else L.lwm_gemv_workspace_bytes)(rows, K, N) for N in Ns)
         ws = _GEMV_WS[key] = torch.empty(need, dtype=torch.uint8, device=x.device)
     ys = [torch.empty(rows, N, dtype=out_dtype, device=x.device) for N in Ns]
     a = _capi.LwmGemvArgs()
@@ -431,13 +441,18 @@ def gemv_fused(x, kernels, *, norm=None, residual=None, want_ss=False, out_dtype
     if want_ss:
         ss_out = torch.empty(rows, Ns[0] // 128, dtype=torch.float32, device=x.device)
         a.ss_out = ss_out.data_ptr()
-    _capi.check(L, L.lwm_gemv_fused_bf16(C.byref(a), _stream_ptr()), "lwm_gemv_fused_bf16")
+    name = "lwm_gemm_rows_fused_bf16" if rows_entry else "lwm_gemv_fused_bf16"
+    _capi.check(L, getattr(L, name)(C.byref(a), _stream_ptr()), name)
     return (ys, ss_out) if want_ss else ys
 
 
 def _decode_rows(x, kernels):
     rows = x.numel() // x.shape[-1]
-    ok = rows <= 4 and x.is_cuda and x.dtype == torch.bfloat16 and x.shape[-1] % 32 == 0 and x.shape[-1] <= 12288 and \
+    if rows > 4:                       # (5..N rows: only where the option is on)
+        limit = decode_rows_limit()
+        if limit is None or rows > limit:
+            return 0
+    ok = x.is_cuda and x.dtype == torch.bfloat16 and x.shape[-1] % 32 == 0 and x.shape[-1] <= 12288 and \
         not (torch.is_grad_enabled() and (x.requires_grad or any(k.requires_grad for k in kernels))) and \
         all(k.dtype == torch.bfloat16 and k.is_contiguous() and k.shape[1] % 8 == 0 for k in kernels)
     return rows if ok else 0
@@ -445,7 +460,8 @@ def _decode_rows(x, kernels):
 
 def dense(x, kernel, out_dtype=None):
     """flax nn.Dense without bias, `x @ kernel` (lwm/llama.py:427-432, :659).  A cached-decode step (at most four
-    rows in all, no autograd) streams the kernel through lwm_gemv_bf16; everything else is the library GEMM."""
+    rows in all, no autograd) streams the kernel through lwm_gemv_bf16 -- 5..N rows through lwm_gemm_rows_fused_bf16 where
+    LWM_DECODE_ROWS=N / model.decode_rows asks for it; everything else is the library GEMM."""
     return dense_multi(x, (kernel,), out_dtype)[0]
 
 
@@ -456,8 +472,13 @@ def dense_multi(x, kernels, out_dtype=None):
     if rows:
         x2 = x.reshape(rows, x.shape[-1])
         out = []
+        if rows > 4 and not rows_x_ok(x2):
+            x2 = x2.clone(memory_format=torch.contiguous_format)
         for i in range(0, len(kernels), 3):
-            out += gemv_multi(x2, list(kernels[i:i + 3]), out_dtype or torch.bfloat16)
+            if rows > 4:
+                out += gemm_rows_fused(x2, list(kernels[i:i + 3]), out_dtype=out_dtype or torch.bfloat16)
+            else:
+                out += gemv_multi(x2, list(kernels[i:i + 3]), out_dtype or torch.bfloat16)
         return [y.reshape(*x.shape[:-1], y.shape[-1]) for y in out]
     if out_dtype in (None, x.dtype):
         return [x @ k for k in kernels]

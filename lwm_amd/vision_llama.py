@@ -10,8 +10,8 @@ import torch
 
 from . import ops as _ops
 from .llama import (LLaMAConfig, LLaMAForCausalLM, _dense, cache_kwargs, capture_decode_step, check_prefill_chunk,
-                    w8_head_logits)
-from .llama_ops import chunked_lm_head_loss, dense
+                    head_logits)
+from .llama_ops import chunked_lm_head_loss
 from .ringattention import sp_size_rank
 
 
@@ -26,9 +26,8 @@ class VideoLLaMAConfig(LLaMAConfig):
 
 
 def _head_logits(model, h, head):
-    """`dense(h, head, torch.float32)`, through the head's 8-bit pack where the model has one (llama.w8_head_logits)"""
-    y = w8_head_logits(model, h, head)
-    return dense(h, head, torch.float32) if y is None else y
+    """`dense(h, head, torch.float32)`, through the head's 8-bit pack where the model has one (llama.head_logits)"""
+    return head_logits(model, h, head)
 
 
 class VideoLLaMAForCausalLM(LLaMAForCausalLM):
@@ -55,8 +54,12 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
 
     def hidden_states(self, input_ids, vision_masks, attention_mask=None, segment_ids=None, position_ids=None,
                       cache=None, layout=None):
-        _, position_ids = self._ring_position_ids(input_ids, position_ids, cache, layout)
+        n_sp, position_ids = self._ring_position_ids(input_ids, position_ids, cache, layout)
         x = self._embed(input_ids, vision_masks)
+        if self.decode_rows is not None:
+            # opt-in (decode_rows / LWM_DECODE_ROWS): a cached one-token step of sample_mode 'text' / 'vision' takes the
+            # fused step of the text model at any row count the option covers -- and with it the 8-bit packs
+            return self._layers(x, n_sp, attention_mask, segment_ids, position_ids, cache, layout)
         fc = self._table(x.device)
         for i, blk in enumerate(self.h):
             x = blk(x, fc, attention_mask, segment_ids, position_ids, None if cache is None else cache[i], layout)

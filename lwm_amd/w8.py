@@ -1,5 +1,5 @@
-"""8-bit (e4m3) decode weights: the torch-tensor front end of lwm_w8_quantise and lwm_gemv_fused_w8 (include/lwm_hip.h,
-"8-bit decode weights"; csrc/gemv_w8.h).  As everything in lwm_amd: hand-written HIP kernels on the current torch stream,
+"""8-bit (e4m3) decode weights: the torch-tensor front end of lwm_w8_quantise, lwm_gemv_fused_w8 and lwm_gemm_rows_fused_w8
+(include/lwm_hip.h, "8-bit decode weights"; csrc/gemv_w8.h, csrc/gemm_rows.h).  As everything in lwm_amd: hand-written HIP kernels on the current torch stream,
 no PyTorch / CPU fallback."""
 import ctypes as C
 
@@ -84,9 +84,25 @@ def gemv_fused_w8(x, packs, *, norm=None, residual=None, want_ss=False, out_dtyp
     share it.  norm = (ss (rows, n <= 64) f32, weight (K,) bf16, eps): RMSNorm on load; residual (rows, N) bf16 (one pack):
     y = bf16(bf16(x @ W) + residual); want_ss: also the (rows, N / 128) partial sums of squares of y.  -> [y_i] or
     ([y_i], ss).  Bit for bit gemv_fused on the rounded kernels."""
+    return _fused_call(False, x, packs, norm, residual, want_ss, out_dtype)
+
+
+def gemm_rows_fused_w8(x, packs, *, norm=None, residual=None, want_ss=False, out_dtype=torch.bfloat16):
+    """llama_ops.gemm_rows_fused over 8-bit packs (lwm_gemm_rows_fused_w8): gemv_fused_w8 for 1..32 rows, the products on the
+    matrix pipe.  Bit for bit gemm_rows_fused on the rounded kernels.  (Callers that hold parameters check each pack
+    against its parameter first: W8Kernel.check, as for gemv_fused_w8.)"""
+    return _fused_call(True, x, packs, norm, residual, want_ss, out_dtype)
+
+
+def _fused_call(rows_entry, x, packs, norm, residual, want_ss, out_dtype):
     rows, K = _check(x, packs, out_dtype)
     n = len(packs)
     Ns = [int(p.shape[1]) for p in packs]
+    if rows_entry:
+        if not 1 <= rows <= 32:
+            raise ValueError(f"gemm_rows_fused_w8: {rows} rows (1..32)")
+        if x.data_ptr() % 16 or x.stride(0) % 8:
+            raise ValueError("gemm_rows_fused_w8: x must be 16-byte aligned with a row stride that is a multiple of 8 elements")
     on = lambda t: _is_dev(t) and t.device == x.device
     if norm is not None:
         ss, w, eps = norm
@@ -102,10 +118,10 @@ def gemv_fused_w8(x, packs, *, norm=None, residual=None, want_ss=False, out_dtyp
     if want_ss and (n != 1 or Ns[0] % 128 or out_dtype != torch.bfloat16):
         raise ValueError("gemv_fused_w8: want_ss goes with ONE pack, a bf16 output and N % 128 == 0")
     L = lib()
-    key = (x.device, rows, K, tuple(Ns))
+    key = (x.device, rows, K, tuple(Ns)) + (("rows",) if rows_entry else ())
     ws = _WS.get(key)
     if ws is None:                     # (one workspace per shape: a hipGraph replays with the pointers it captured)
-        need = sum(L.lwm_gemv_workspace_bytes(rows, K, N) for N in Ns)
+        need = sum((L.lwm_gemm_rows_workspace_bytes if rows_entry else L.lwm_gemv_workspace_bytes)(rows, K, N) for N in Ns)
         ws = _WS[key] = torch.empty(max(need, 16), dtype=torch.uint8, device=x.device)
     ys = [torch.empty(rows, N, dtype=out_dtype, device=x.device) for N in Ns]
     a = _capi.LwmGemvW8Args()
@@ -125,5 +141,6 @@ def gemv_fused_w8(x, packs, *, norm=None, residual=None, want_ss=False, out_dtyp
     if want_ss:
         ss_out = torch.empty(rows, Ns[0] // 128, dtype=torch.float32, device=x.device)
         a.ss_out = ss_out.data_ptr()
-    _capi.check(L, L.lwm_gemv_fused_w8(C.byref(a), _stream_ptr()), "lwm_gemv_fused_w8")
+    name = "lwm_gemm_rows_fused_w8" if rows_entry else "lwm_gemv_fused_w8"
+    _capi.check(L, getattr(L, name)(C.byref(a), _stream_ptr()), name)
     return (ys, ss_out) if want_ss else ys
