@@ -423,6 +423,61 @@ typedef struct LwmKv8PrefillArgs {
 } LwmKv8PrefillArgs;
 int lwm_attn_prefill_kv8(const LwmKv8PrefillArgs* args, void* stream);
 
+/* ------------------------------------------------------------------ 4-bit KV cache (lwm_version() >= 570)
+ * The cache in the OCP MXFP4 format: e2m1 codes with one e8m0 scale byte per block of 32 elements.  68 bytes per
+ * (row, head) against 256 for bf16 and 132 for the 8-bit cache: 0.27 of the bf16 cache's bytes, in memory and per
+ * decode step.  Per layer four tensors:
+ *   cached_key, cached_value          uint8 (B, max_length, H, 64): two e2m1 codes per byte, element 2i in the low
+ *                                     nibble and element 2i+1 in the high nibble; heads of a row contiguous;
+ *   key_scale_e8m0, value_scale_e8m0  uint8 (B, max_length, H, 4): one e8m0 byte b per block of 32 consecutive
+ *                                     elements of a head, the scale 2^(b - 127).
+ * e2m1: the sign in bit 3; the magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6 for the codes 0..7.
+ * One block (32 bf16 values x): amax = max |x|; s = the smallest power of two with amax / s <= 6, its biased
+ * exponent clamped to [1, 254] (s >= 2^-126; byte 255 is never written), s = 1 (byte 127) when amax == 0;
+ * q = e2m1(x / s), round to nearest, ties to the even code (x / s is exact in f32 and in range: nothing saturates;
+ * -0 keeps its sign).  This is the 8-bit cache's rule with 6 in place of 448, not the OCP "floor(log2 amax) - 2"
+ * rule, which saturates.  q * s is exactly representable in bf16, a normal number whenever s >= 2^-125.  Non-finite
+ * inputs are not supported.
+ *
+ * lwm_kv4_cache_write / _at: the arguments of lwm_kv8_cache_write / _at (row_elems = H * 128; cache and scale batch
+ * strides in bytes, src strides in bf16 elements); rows of a batch entry are contiguous (H * 64 and H * 4 bytes).
+ * src 16-byte aligned, cache and scale 4-byte aligned; otherwise LWM_EINVAL. */
+int lwm_kv4_cache_write(void* cache, const void* src, int32_t B, int64_t cache_stride_b,
+                        int64_t src_stride_b, int64_t dst_row0, int64_t src_row0, int64_t nrows,
+                        int32_t row_elems, void* scale, int64_t scale_stride_b, int32_t H, void* stream);
+int lwm_kv4_cache_write_at(void* cache, const void* src, int32_t B, int64_t cache_stride_b,
+                           int64_t src_stride_b, const int32_t* dst_row0_dev, int64_t row_offset,
+                           int64_t cache_rows, int64_t src_row0, int64_t nrows, int32_t row_elems,
+                           void* scale, int64_t scale_stride_b, int32_t H, void* stream);
+
+/* Cached-decode attention (one query per batch row) over that cache: the contract of lwm_attn_decode_kv8.  The
+ * visible key range of each (B, Sk) mask row is partitioned over k_splits pieces, one workgroup each; masked keys
+ * inside it contribute nothing whatever their nibbles and scale bytes hold (0xFF included); the normalised partials
+ * out_acc [k_splits,B,1,H,D] f32 and lse_acc [k_splits,B,H,1] f32 are merged by lwm_attn_combine; a row with nothing
+ * visible gives (0, -inf).  The score of a key is the sum over its four blocks of scale_b * (q_b . k_b).
+ * D = 128; q, the cache rows (k/v_stride_* in bytes, a head is 64 contiguous bytes) and out_acc 16-byte aligned;
+ * scale strides in bytes, the 4 bytes of a head and the H heads of a row contiguous; 0 <= k_splits <= 4096.
+ * Anything else is LWM_EINVAL with a message.  Chunked prefill (a block of queries) over this cache is not built. */
+typedef struct LwmKv4DecodeArgs {
+    LwmTensor4 q;                   /* bf16 (B,1,H,D) */
+    const void* k;                  /* nibble bytes (B,Sk,H,D/2) */
+    const void* v;
+    int64_t k_stride_b, k_stride_s, k_stride_h;
+    int64_t v_stride_b, v_stride_s, v_stride_h;
+    const void* k_scale;            /* e8m0 bytes (B,Sk,H,4) */
+    const void* v_scale;
+    int64_t k_scale_stride_b, k_scale_stride_s;
+    int64_t v_scale_stride_b, v_scale_stride_s;
+    const uint8_t* dense_mask;      /* (B,Sk) u8, nonzero = visible; NULL = all visible */
+    int64_t mask_stride_b;
+    int32_t B, Sk, H, D;
+    float scale;                    /* softmax scale, > 0 */
+    int32_t k_splits;
+    float* out_acc;
+    float* lse_acc;
+} LwmKv4DecodeArgs;
+int lwm_attn_decode_kv4(const LwmKv4DecodeArgs* args, void* stream);
+
 /* Elementwise helpers of the ring driver (HBM-bound). */
 /* dst_bf16[n] = (bf16) src_f32[n] */
 int lwm_cast_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream);
@@ -737,7 +792,8 @@ const char* lwm_last_error(void);
 int lwm_version(void);
 /* sizeof(LwmAttnArgs) (which = 0) / sizeof(LwmConvArgs) (1) / sizeof(LwmRingArgs) (2) / sizeof(LwmGemvArgs) (3) /
  * sizeof(LwmSampleArgs) (4) / sizeof(LwmKv8DecodeArgs) (5) / sizeof(LwmKv8PrefillArgs) (6) / sizeof(LwmAdamWArgs) (7) as
- * sizeof(LwmAdamWTensor) (8: an element of a device table that the caller lays out) / sizeof(LwmGemvW8Args) (9) as
+ * sizeof(LwmAdamWTensor) (8: an element of a device table that the caller lays out) / sizeof(LwmGemvW8Args) (9) /
+ * sizeof(LwmKv4DecodeArgs) (10) as
  * compiled into the library:
  * lets a foreign-language binding verify its struct mirror at load time. */
 int lwm_sizeof(int which);

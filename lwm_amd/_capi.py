@@ -113,6 +113,11 @@ class LwmKv8DecodeArgs(C.Structure):
     ]
 
 
+class LwmKv4DecodeArgs(C.Structure):
+    """the field list of LwmKv8DecodeArgs; the scales are e8m0 bytes and their strides are in bytes"""
+    _fields_ = list(LwmKv8DecodeArgs._fields_)
+
+
 class LwmKv8PrefillArgs(C.Structure):
     _fields_ = [
         ("q", LwmTensor4), ("k", C.c_void_p), ("v", C.c_void_p),
@@ -229,6 +234,12 @@ PROTOTYPES = {
                                          C.c_void_p]),
     "lwm_attn_decode_kv8": (C.c_int, [C.POINTER(LwmKv8DecodeArgs), C.c_void_p]),
     "lwm_attn_prefill_kv8": (C.c_int, [C.POINTER(LwmKv8PrefillArgs), C.c_void_p]),
+    "lwm_kv4_cache_write": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
+                                     C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
+    "lwm_kv4_cache_write_at": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                         C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
+                                         C.c_void_p]),
+    "lwm_attn_decode_kv4": (C.c_int, [C.POINTER(LwmKv4DecodeArgs), C.c_void_p]),
     "lwm_rope_bf16": (C.c_int, [LwmTensor4, LwmTensor4, C.c_void_p, C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p]),
     "lwm_rmsnorm_fwd_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
                                       C.c_float, C.c_void_p]),
@@ -283,7 +294,8 @@ def bind(lib):
         fn.restype = res
         fn.argtypes = args
     for which, cls in ((0, LwmAttnArgs), (1, LwmConvArgs), (2, LwmRingArgs), (4, LwmSampleArgs), (5, LwmKv8DecodeArgs),
-                       (6, LwmKv8PrefillArgs), (7, LwmAdamWArgs), (8, LwmAdamWTensor), (9, LwmGemvW8Args)):
+                       (6, LwmKv8PrefillArgs), (7, LwmAdamWArgs), (8, LwmAdamWTensor), (9, LwmGemvW8Args),
+                       (10, LwmKv4DecodeArgs)):
         if lib.lwm_sizeof(which) != C.sizeof(cls):
             raise ImportError(f"{cls.__name__}: ctypes mirror is {C.sizeof(cls)} bytes, library has "
                               f"{lib.lwm_sizeof(which)} (include/lwm_hip.h and lwm_amd/_capi.py out of step)")

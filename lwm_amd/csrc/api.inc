@@ -6,6 +6,7 @@
 #include "sample.h"
 #include "optim.h"
 #include "attn_decode_kv8.h"
+#include "attn_decode_kv4.h"
 #include "attn_prefill_kv8.h"
 #include "gemv_w8.h"
 #include "gemm_rows.h"
@@ -287,6 +288,96 @@ int lwm_attn_decode_kv8(const LwmKv8DecodeArgs* a, void* stream) {
     p.B = a->B; p.Sk = a->Sk; p.H = a->H; p.k_splits = a->k_splits > 1 ? a->k_splits : 1;
     p.scale = a->scale; p.out_acc = a->out_acc; p.lse_acc = a->lse_acc;
     return launch("attn_decode_kv8", attn_decode_kv8_kernel, (long)p.B * p.k_splits, kDecThreads, kDec8LdsBytes, stream, p);
+}
+
+static int kv4_write_params(const char* name, lwm::Kv4WriteParams* p, void* cache, const void* src, int32_t B,
+                            int64_t cache_stride_b, int64_t src_stride_b, int64_t src_row0, int64_t nrows,
+                            int32_t row_elems, void* scale, int64_t scale_stride_b, int32_t H) {
+    using namespace lwm;
+    if (!cache || !src || !scale) return fail(LWM_EINVAL, "%s: null pointer", name);
+    if (B < 0 || nrows < 0 || H <= 0 || src_row0 < 0 || cache_stride_b < 0 || scale_stride_b < 0 || src_stride_b < 0)
+        return fail(LWM_EINVAL, "%s: bad dimension", name);
+    if (row_elems != H * kHeadDim)
+        return fail(LWM_EINVAL, "%s: row_elems = %ld, H * 128 = %ld (head_dim is 128)", name, (long)row_elems, (long)H * kHeadDim);
+    if (!aligned16(src) || (src_stride_b & 7) || (((uintptr_t)cache | (uintptr_t)cache_stride_b | (uintptr_t)scale_stride_b) & 3) ||
+        (((uintptr_t)scale) & 3))
+        return fail(LWM_EINVAL, "%s: misaligned (src rows 16-byte aligned, cache and scale rows 4-byte)", name);
+    p->cache = (uint8_t*)cache; p->scale = (uint8_t*)scale; p->src = (const bf16_t*)src;
+    p->cache_sb = cache_stride_b; p->scale_sb = scale_stride_b; p->src_sb = src_stride_b;
+    p->row0_dev = nullptr; p->dst_row0 = 0; p->cache_rows = 0;
+    p->src_row0 = src_row0; p->nrows = nrows; p->B = B; p->H = H;
+    return 0;
+}
+
+static long kv4_write_blocks(const lwm::Kv4WriteParams& p) {
+    const int64_t blocks = ((int64_t)p.B * p.nrows * p.H * 16 + 255) / 256;
+    return (long)(blocks > 16384 ? 16384 : blocks);
+}
+
+int lwm_kv4_cache_write(void* cache, const void* src, int32_t B, int64_t cache_stride_b,
+                        int64_t src_stride_b, int64_t dst_row0, int64_t src_row0, int64_t nrows,
+                        int32_t row_elems, void* scale, int64_t scale_stride_b, int32_t H, void* stream) {
+    using namespace lwm;
+    Kv4WriteParams p;
+    int r;
+    if ((r = kv4_write_params("kv4_cache_write", &p, cache, src, B, cache_stride_b, src_stride_b, src_row0, nrows,
+                              row_elems, scale, scale_stride_b, H))) return r;
+    if (dst_row0 < 0) return fail(LWM_EINVAL, "%s", "kv4_cache_write: bad dimension");
+    if (B == 0 || nrows == 0) return LWM_OK;
+    p.dst_row0 = dst_row0;
+    p.cache_rows = dst_row0 + nrows;              // the caller has checked the range against its cache
+    return launch("kv4_quant_write", kv4_quant_write_kernel, kv4_write_blocks(p), 256, 0, stream, p);
+}
+
+int lwm_kv4_cache_write_at(void* cache, const void* src, int32_t B, int64_t cache_stride_b,
+                           int64_t src_stride_b, const int32_t* dst_row0_dev, int64_t row_offset,
+                           int64_t cache_rows, int64_t src_row0, int64_t nrows, int32_t row_elems,
+                           void* scale, int64_t scale_stride_b, int32_t H, void* stream) {
+    using namespace lwm;
+    Kv4WriteParams p;
+    int r;
+    if ((r = kv4_write_params("kv4_cache_write_at", &p, cache, src, B, cache_stride_b, src_stride_b, src_row0, nrows,
+                              row_elems, scale, scale_stride_b, H))) return r;
+    if (!dst_row0_dev) return fail(LWM_EINVAL, "%s", "kv4_cache_write_at: null pointer");
+    if (cache_rows < 0) return fail(LWM_EINVAL, "%s", "kv4_cache_write_at: bad dimension");
+    if (B == 0 || nrows == 0) return LWM_OK;
+    p.row0_dev = dst_row0_dev;
+    p.dst_row0 = row_offset;
+    p.cache_rows = cache_rows;
+    return launch("kv4_quant_write_at", kv4_quant_write_at_kernel, kv4_write_blocks(p), 256, 0, stream, p);
+}
+
+int lwm_attn_decode_kv4(const LwmKv4DecodeArgs* a, void* stream) {
+    using namespace lwm;
+    if (!a) return fail(LWM_EINVAL, "%s", "attn_decode_kv4: args is null");
+    int r;
+    if ((r = check_t4("q", a->q, true))) return r;
+    if (a->D != kHeadDim) return fail(LWM_EINVAL, "%s: head_dim %ld (only 128)", "attn_decode_kv4", a->D);
+    if (a->B < 0 || a->Sk < 0 || a->H <= 0) return fail(LWM_EINVAL, "%s", "attn_decode_kv4: bad dimension");
+    if (!(a->scale > 0.0f)) return fail(LWM_EINVAL, "%s", "attn_decode_kv4: scale must be > 0");
+    if (!a->k || !a->v || !a->k_scale || !a->v_scale || !a->out_acc || !a->lse_acc)
+        return fail(LWM_EINVAL, "%s", "attn_decode_kv4: null pointer (k, v, k_scale, v_scale, out_acc, lse_acc)");
+    if (!aligned16(a->k) || !aligned16(a->v) || !aligned16(a->out_acc) || ((a->k_stride_b | a->k_stride_s | a->k_stride_h |
+                                                                          a->v_stride_b | a->v_stride_s | a->v_stride_h) & 15))
+        return fail(LWM_EINVAL, "%s", "attn_decode_kv4: cache rows and out_acc must be 16-byte aligned (pointers and strides)");
+    if (a->k_stride_s < 0 || a->v_stride_s < 0 || a->k_stride_h < 64 || a->v_stride_h < 64 || a->k_scale_stride_s < 0 ||
+        a->v_scale_stride_s < 0 || a->k_scale_stride_b < 0 || a->v_scale_stride_b < 0 || a->k_stride_b < 0 || a->v_stride_b < 0)
+        return fail(LWM_EINVAL, "%s", "attn_decode_kv4: bad strides (non-negative; a head is 64 bytes)");
+    if (((uintptr_t)a->lse_acc) & 3) return fail(LWM_EINVAL, "%s", "attn_decode_kv4: lse_acc must be 4-byte aligned");
+    if (a->k_splits < 0 || a->k_splits > 4096) return fail(LWM_EINVAL, "%s", "attn_decode_kv4: k_splits out of range");
+    if (a->B == 0) return LWM_OK;
+    Kv4DecodeParams p;
+    p.q = (const bf16_t*)a->q.ptr; p.q_sb = a->q.stride_b; p.q_sh = a->q.stride_h;
+    p.k = (const uint8_t*)a->k; p.v = (const uint8_t*)a->v;
+    p.k_scale = (const uint8_t*)a->k_scale; p.v_scale = (const uint8_t*)a->v_scale;
+    p.k_sb = a->k_stride_b; p.k_ss = a->k_stride_s; p.k_sh = a->k_stride_h;
+    p.v_sb = a->v_stride_b; p.v_ss = a->v_stride_s; p.v_sh = a->v_stride_h;
+    p.ks_sb = a->k_scale_stride_b; p.ks_ss = a->k_scale_stride_s;
+    p.vs_sb = a->v_scale_stride_b; p.vs_ss = a->v_scale_stride_s;
+    p.dense_mask = a->dense_mask; p.msk_sb = a->mask_stride_b;
+    p.B = a->B; p.Sk = a->Sk; p.H = a->H; p.k_splits = a->k_splits > 1 ? a->k_splits : 1;
+    p.scale = a->scale; p.out_acc = a->out_acc; p.lse_acc = a->lse_acc;
+    return launch("attn_decode_kv4", attn_decode_kv4_kernel, (long)p.B * p.k_splits, kDecThreads, kDec4LdsBytes, stream, p);
 }
 
 int lwm_attn_prefill_kv8(const LwmKv8PrefillArgs* a, void* stream) {
@@ -963,9 +1054,9 @@ int lwm_adamw_step(const LwmAdamWArgs* a, void* stream) {
 int lwm_adamw_chunk(void) { return lwm::kAdamWChunk; }
 
 const char* lwm_last_error(void) { return lwm::g_err; }
-int lwm_version(void) { return 560; }
+int lwm_version(void) { return 570; }
 int lwm_sizeof(int which) {
-    return which == 0 ? (int)sizeof(LwmAttnArgs) : which == 1 ? (int)sizeof(LwmConvArgs) : which == 2 ? (int)sizeof(LwmRingArgs) : which == 3 ? (int)sizeof(LwmGemvArgs) : which == 4 ? (int)sizeof(LwmSampleArgs) : which == 5 ? (int)sizeof(LwmKv8DecodeArgs) : which == 6 ? (int)sizeof(LwmKv8PrefillArgs) : which == 7 ? (int)sizeof(LwmAdamWArgs) : which == 8 ? (int)sizeof(LwmAdamWTensor) : which == 9 ? (int)sizeof(LwmGemvW8Args) : -1;
+    return which == 0 ? (int)sizeof(LwmAttnArgs) : which == 1 ? (int)sizeof(LwmConvArgs) : which == 2 ? (int)sizeof(LwmRingArgs) : which == 3 ? (int)sizeof(LwmGemvArgs) : which == 4 ? (int)sizeof(LwmSampleArgs) : which == 5 ? (int)sizeof(LwmKv8DecodeArgs) : which == 6 ? (int)sizeof(LwmKv8PrefillArgs) : which == 7 ? (int)sizeof(LwmAdamWArgs) : which == 8 ? (int)sizeof(LwmAdamWTensor) : which == 9 ? (int)sizeof(LwmGemvW8Args) : which == 10 ? (int)sizeof(LwmKv4DecodeArgs) : -1;
 }
 
 }  // extern "C"

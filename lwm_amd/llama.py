@@ -241,6 +241,8 @@ class LLaMAAttention(torch.nn.Module):
         ck, cv = cache["cached_key"], cache["cached_value"]
         if "key_scale" in cache:
             return self._cached_kv8(xq, xk, xv, attention_mask, cache)
+        if "key_scale_e8m0" in cache:
+            return self._cached_kv4(xq, xk, xv, attention_mask, cache)
         if "index_dev" in cache:
             # hipGraph-capturable decode step: cache_index lives on the device (one int32 shared by all
             # layers), the mask was built from it once for this step, and the new row is written by
@@ -330,6 +332,53 @@ class LLaMAAttention(torch.nn.Module):
             cache["cache_index"] = idx + 1
             mask = cached_visibility(B, 1, max_len, idx, attention_mask, xq.device)[:, 0].to(torch.uint8).contiguous()
         o_parts, l_parts = _ops.attn_decode_kv8(xq, ck, ks, cv, vs, k_splits=_pick_splits(B, 1, H, max_len), dense_mask=mask)
+        return _ops.attn_combine(o_parts, l_parts, want_bf16=True)[0]
+
+
+    def _cached_kv4(self, xq, xk, xv, attention_mask, cache):
+        """_cached over a 4-bit cache (init_cache(kv_dtype="fp4"): e2m1 nibbles + one e8m0 byte per block of 32,
+        csrc/attn_decode_kv4.h), by the rules of _cached_kv8.  Prefill (cache_index == 0): the block attends over its OWN
+        bf16 keys and values under the same structured mask and is quantised into the cache afterwards.  A decode step
+        quantises its row, then streams the cache (lwm_attn_decode_kv4 + the split-K combine).  A block at
+        cache_index > 0 is refused: a block kernel over the 4-bit cache is not built."""
+        from .ring import _pick_splits
+        from . import kv4 as _kv4
+        B, Q, H, D = xq.shape
+        ck, cv, ks, vs = cache["cached_key"], cache["cached_value"], cache["key_scale_e8m0"], cache["value_scale_e8m0"]
+        if xq.dtype != torch.bfloat16:
+            raise NotImplementedError("kv_dtype='fp4' with a float32 model: the 4-bit cache quantises bf16 rows and its "
+                                      "decode kernel takes a bf16 query (--dtype=bf16, or the default cache)")
+        if sp_size_rank("sp")[0] > 1:
+            raise NotImplementedError("kv_dtype='fp4' with sp > 1: the 4-bit cache is not sharded over the sequence ring "
+                                      "(one rank, or the default cache)")
+        if D != 128:
+            raise NotImplementedError(f"kv_dtype='fp4': head_dim {D} (the 4-bit decode kernel is built for 128)")
+        xq, xk, xv = xq.contiguous(), xk.contiguous(), xv.contiguous()
+        max_len = ck.shape[1]
+        blocks = ("kv_dtype='fp4' with Q > 1 at cache_index > 0: the 4-bit cache takes a prompt at cache_index 0 and one "
+                  "token per step after it (a block kernel over the 4-bit cache is not built)")
+        if "index_dev" in cache:                   # hipGraph-capturable step: see _cached
+            if Q != 1:
+                raise NotImplementedError(blocks)
+            _kv4.kv4_cache_write_at(ck, ks, xk, cache["index_dev"])
+            _kv4.kv4_cache_write_at(cv, vs, xv, cache["index_dev"])
+            mask = (cache["mask_dev"][:, 0] != 0).to(torch.uint8).contiguous()
+        else:
+            idx = int(cache["cache_index"])
+            if idx == 0:
+                kvld = None if attention_mask is None else attention_mask[:, :Q]
+                out = ringattention_inference(xq, xk, xv, None, axis_name="sp", causal_offset=0, key_valid=kvld)
+                _kv4.kv4_cache_write(ck, ks, xk, dst_row0=0)
+                _kv4.kv4_cache_write(cv, vs, xv, dst_row0=0)
+                cache["cache_index"] = Q
+                return out
+            if Q != 1:
+                raise NotImplementedError(blocks)
+            _kv4.kv4_cache_write(ck, ks, xk, dst_row0=idx)
+            _kv4.kv4_cache_write(cv, vs, xv, dst_row0=idx)
+            cache["cache_index"] = idx + 1
+            mask = cached_visibility(B, 1, max_len, idx, attention_mask, xq.device)[:, 0].to(torch.uint8).contiguous()
+        o_parts, l_parts = _kv4.attn_decode_kv4(xq, ck, ks, cv, vs, k_splits=_pick_splits(B, 1, H, max_len), dense_mask=mask)
         return _ops.attn_combine(o_parts, l_parts, want_bf16=True)[0]
 
 
@@ -545,15 +594,35 @@ class LLaMAForCausalLM(torch.nn.Module):
         prefill, a follow-up turn): such a block is quantised into the cache first and then attends over the quantised
         rows, its own included -- the decode step's rule, so a block equals its tokens fed one at a time, whereas a block
         at cache_index 0 sees its own unquantised keys.  Opt-in because of that difference.  The default cache takes blocks
-        anywhere as it is; the flag changes nothing for it."""
+        anywhere as it is; the flag changes nothing for it.
+        kv_dtype="fp4" (extension): the 4-bit MXFP4 cache of csrc/attn_decode_kv4.h -- per layer cached_key / cached_value
+        as uint8 (B, max_length, H, 64) e2m1 nibble pairs plus key_scale_e8m0 / value_scale_e8m0 (B, max_length, H, 4) e8m0
+        bytes: 0.27 of the bytes.  bf16 models on one rank; a prompt at cache_index 0, then one token per step;
+        chunked_prefill=True is refused (a block kernel over the 4-bit cache is not built)."""
         device = device or self.wte.device
         H = self.cfg.num_attention_heads
         D = self.cfg.hidden_size // H
         n_sp = sp_size_rank("sp")[0]
         if max_length % n_sp:
             raise ValueError(f"max_length {max_length} is not divisible by the sp ring size {n_sp}")
-        if kv_dtype not in (None, "fp8"):
-            raise ValueError(f"kv_dtype={kv_dtype!r}: None (the model's dtype) or 'fp8'")
+        if kv_dtype not in (None, "fp8", "fp4"):
+            raise ValueError(f"kv_dtype={kv_dtype!r}: None (the model's dtype), 'fp8' or 'fp4'")
+        if kv_dtype == "fp4":
+            if self.dtype != torch.bfloat16:
+                raise NotImplementedError("kv_dtype='fp4' with a float32 model: the 4-bit cache quantises bf16 rows and its "
+                                          "decode kernel takes a bf16 query (--dtype=bf16, or the default cache)")
+            if n_sp > 1:
+                raise NotImplementedError("kv_dtype='fp4' with sp > 1: the 4-bit cache is not sharded over the sequence ring "
+                                          "(one rank, or the default cache)")
+            if D != 128:
+                raise NotImplementedError(f"kv_dtype='fp4': head_dim {D} (the 4-bit decode kernel is built for 128)")
+            if chunked_prefill:
+                raise NotImplementedError("kv_dtype='fp4' with chunked prefill (chunked_prefill=True, prefill_chunk=N): a block "
+                                          "kernel over the 4-bit cache is not built; kv_dtype='fp8' takes blocks")
+            q = lambda: torch.zeros(batch_size, max_length, H, D // 2, dtype=torch.uint8, device=device)
+            sc = lambda: torch.full((batch_size, max_length, H, 4), 127, dtype=torch.uint8, device=device)
+            return [dict(cached_key=q(), cached_value=q(), key_scale_e8m0=sc(), value_scale_e8m0=sc(), cache_index=0)
+                    for _ in self.h]
         if kv_dtype == "fp8":
             if self.dtype != torch.bfloat16:
                 raise NotImplementedError("kv_dtype='fp8' with a float32 model: the 8-bit cache quantises bf16 rows and its "
@@ -591,7 +660,8 @@ class LLaMAForCausalLM(torch.nn.Module):
         issued one by one.  Single-rank only (the cross-rank combine is not captured).
 
         kv_dtype="fp8": the 8-bit KV cache (init_cache); the prompt attends over its own bf16 keys, every later
-        step over the quantised cache.  Works with graph=True.
+        step over the quantised cache.  Works with graph=True.  kv_dtype="fp4": the 4-bit MXFP4 cache, by the same
+        rules; prefill_chunk is refused with it (a block kernel over the 4-bit cache is not built).
 
         prefill_chunk=N: the prompt goes through the layers in blocks of N tokens (the last may be shorter), so the
         transient activations of the prefill are bounded by N instead of the prompt length.  With kv_dtype="fp8" the
@@ -733,8 +803,8 @@ def cache_kwargs(kv_dtype, prefill_chunk=None):
     """The keyword arguments of init_cache for a generate() call: only what is non-default is passed, so that a stand-in
     model with the three-argument init_cache keeps working."""
     kw = {} if kv_dtype is None else dict(kv_dtype=kv_dtype)
-    if kv_dtype == "fp8" and prefill_chunk is not None:
-        kw["chunked_prefill"] = True
+    if kv_dtype in ("fp8", "fp4") and prefill_chunk is not None:
+        kw["chunked_prefill"] = True             # (init_cache refuses it for 'fp4', by name)
     return kw
 
 

@@ -224,7 +224,8 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
         token drawn on the device by ops.sample_tokens from the Philox stream of `seed` (bf16 or float32 models);
         seed= with graph=True = the same one-token step captured once in a hipGraph and replayed (bf16, one rank).
         With a seed the loop reads `done` back every DONE_CHECK_EVERY tokens instead of after every token.
-        kv_dtype="fp8": the 8-bit KV cache (LLaMAModel.init_cache), on every one of these routes.  prefill_chunk=N: the
+        kv_dtype="fp8": the 8-bit KV cache (LLaMAModel.init_cache), on every one of these routes.  kv_dtype="fp4": the 4-bit
+        MXFP4 cache, likewise (no prefill_chunk with it: a block kernel over the 4-bit cache is not built).  prefill_chunk=N: the
         prompt in blocks of N tokens (LLaMAForCausalLM.generate), on every one of these routes too."""
         if self.cfg.sample_mode != "text":
             raise ValueError("generate() decodes text: set sample_mode='text' (scripts/run_vision_chat.sh)")
@@ -271,8 +272,8 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
 
         Sampling as generate(): generator= = the torch sampler, eager; seed= = ops.sample_tokens on the device, which
         also mixes the halves, forces the end-of-frame code and feeds both halves; seed= with graph=True = that step
-        captured once in a hipGraph and replayed (bf16, one rank).  kv_dtype="fp8": the 8-bit KV cache; prefill_chunk=N: the
-        prompt in blocks of N tokens (LLaMAForCausalLM.generate)."""
+        captured once in a hipGraph and replayed (bf16, one rank).  kv_dtype="fp8" / "fp4": the 8-bit / 4-bit KV cache;
+        prefill_chunk=N: the prompt in blocks of N tokens (LLaMAForCausalLM.generate)."""
         if self.cfg.sample_mode != "vision":
             raise ValueError("generate_vision() needs sample_mode='vision' (scripts/run_sample_image.sh)")
         B2, S = input_ids.shape
