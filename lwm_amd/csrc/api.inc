@@ -5,6 +5,7 @@
 // misc_kernels.h and "lwm_hip.h" already included.
 #include "sample.h"
 #include "optim.h"
+#include "attn_decode_kvq.h"
 #include "attn_decode_kv8.h"
 #include "attn_decode_kv4.h"
 #include "attn_prefill_kv8.h"
@@ -96,6 +97,78 @@ static AttnParams to_params(const LwmAttnArgs* a) {
         p.dqa_sh = kHeadDim; p.dqa_ss = (int64_t)a->H * kHeadDim; p.dqa_sb = (int64_t)a->Sq * a->H * kHeadDim;
     }
     return p;
+}
+
+// The entries of the two quantised caches (attn_decode_kv8.h, attn_decode_kv4.h) share their checks.  What differs per
+// entry is passed in: the names, the kernel, the code that its shape and alignment refusals return, and the alignment
+// rule.  `at`: the destination row comes from device memory (row0_dev) and dst_row0 is the offset added to it.
+template <class P>
+static int kvq_cache_write(const char* name, const char* kname, void (*kernel)(P), bool at, int ecode,
+                           int cache_align, int scale_stride_align, const char* align_rule, void* cache, const void* src,
+                           int32_t B, int64_t cache_stride_b, int64_t src_stride_b, const int32_t* row0_dev, int64_t dst_row0,
+                           int64_t cache_rows, int64_t src_row0, int64_t nrows, int32_t row_elems, void* scale,
+                           int64_t scale_stride_b, int32_t H, void* stream) {
+    if (!cache || !src || !scale) return fail(LWM_EINVAL, "%s: null pointer", name);
+    if (B < 0 || nrows < 0 || H <= 0 || src_row0 < 0 || cache_stride_b < 0 || scale_stride_b < 0 || src_stride_b < 0)
+        return fail(LWM_EINVAL, "%s: bad dimension", name);
+    if (row_elems != H * kHeadDim)
+        return fail(ecode, "%s: row_elems = %ld, H * 128 = %ld (head_dim is 128)", name, (long)row_elems, (long)H * kHeadDim);
+    if (!aligned16(src) || (src_stride_b & 7) || (((uintptr_t)cache | (uintptr_t)cache_stride_b) & (cache_align - 1)) ||
+        (((uintptr_t)scale) & 3) || (scale_stride_b & (scale_stride_align - 1)))
+    {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "%s: misaligned (%s)", name, align_rule);
+        return fail(ecode, "%s", msg);
+    }
+    if (at && !row0_dev) return fail(LWM_EINVAL, "%s: null pointer", name);
+    if (at ? cache_rows < 0 : dst_row0 < 0) return fail(LWM_EINVAL, "%s: bad dimension", name);
+    if (B == 0 || nrows == 0) return LWM_OK;
+    P p;
+    p.cache = (uint8_t*)cache; p.scale = (decltype(p.scale))scale; p.src = (const bf16_t*)src;
+    p.cache_sb = cache_stride_b; p.scale_sb = scale_stride_b; p.src_sb = src_stride_b;
+    p.row0_dev = row0_dev; p.dst_row0 = dst_row0;
+    p.cache_rows = at ? cache_rows : dst_row0 + nrows;          // host index: the caller has checked the range against its cache
+    p.src_row0 = src_row0; p.nrows = nrows; p.B = B; p.H = H;
+    const int64_t blocks = ((int64_t)B * nrows * H * 16 + 255) / 256;
+    return launch(kname, kernel, (long)(blocks > 16384 ? 16384 : blocks), 256, 0, stream, p);
+}
+
+// head_bytes > 0: the strides are checked too (non-negative, a head no smaller than that).  scales_f32: the scale
+// pointers are checked for 4-byte alignment with lse_acc.
+template <class F, class P, class Args>
+static int kvq_attn_decode(const char* name, void (*kernel)(P), int ecode, int head_bytes, bool scales_f32,
+                           const Args* a, void* stream) {
+    if (!a) return fail(LWM_EINVAL, "%s: args is null", name);
+    int r;
+    if ((r = check_t4("q", a->q, true))) return r;
+    if (a->D != kHeadDim) return fail(ecode, "%s: head_dim %ld (only 128)", name, a->D);
+    if (a->B < 0 || a->Sk < 0 || a->H <= 0) return fail(LWM_EINVAL, "%s: bad dimension", name);
+    if (!(a->scale > 0.0f)) return fail(LWM_EINVAL, "%s: scale must be > 0", name);
+    if (!a->k || !a->v || !a->k_scale || !a->v_scale || !a->out_acc || !a->lse_acc)
+        return fail(LWM_EINVAL, "%s: null pointer (k, v, k_scale, v_scale, out_acc, lse_acc)", name);
+    if (!aligned16(a->k) || !aligned16(a->v) || !aligned16(a->out_acc) || ((a->k_stride_b | a->k_stride_s | a->k_stride_h |
+                                                                          a->v_stride_b | a->v_stride_s | a->v_stride_h) & 15))
+        return fail(ecode, "%s: cache rows and out_acc must be 16-byte aligned (pointers and strides)", name);
+    if (head_bytes > 0 &&
+        (a->k_stride_s < 0 || a->v_stride_s < 0 || a->k_stride_h < head_bytes || a->v_stride_h < head_bytes || a->k_scale_stride_s < 0 ||
+         a->v_scale_stride_s < 0 || a->k_scale_stride_b < 0 || a->v_scale_stride_b < 0 || a->k_stride_b < 0 || a->v_stride_b < 0))
+        return fail(LWM_EINVAL, "%s: bad strides (non-negative; a head is %ld bytes)", name, (long)head_bytes);
+    if (((scales_f32 ? (uintptr_t)a->k_scale | (uintptr_t)a->v_scale : 0) | (uintptr_t)a->lse_acc) & 3)
+        return fail(ecode, scales_f32 ? "%s: scales and lse_acc must be 4-byte aligned" : "%s: lse_acc must be 4-byte aligned", name);
+    if (a->k_splits < 0 || a->k_splits > 4096) return fail(LWM_EINVAL, "%s: k_splits out of range", name);
+    if (a->B == 0) return LWM_OK;
+    P p;
+    p.q = (const bf16_t*)a->q.ptr; p.q_sb = a->q.stride_b; p.q_sh = a->q.stride_h;
+    p.k = (const uint8_t*)a->k; p.v = (const uint8_t*)a->v;
+    p.k_scale = (const typename F::scale_t*)a->k_scale; p.v_scale = (const typename F::scale_t*)a->v_scale;
+    p.k_sb = a->k_stride_b; p.k_ss = a->k_stride_s; p.k_sh = a->k_stride_h;
+    p.v_sb = a->v_stride_b; p.v_ss = a->v_stride_s; p.v_sh = a->v_stride_h;
+    p.ks_sb = a->k_scale_stride_b; p.ks_ss = a->k_scale_stride_s;
+    p.vs_sb = a->v_scale_stride_b; p.vs_ss = a->v_scale_stride_s;
+    p.dense_mask = a->dense_mask; p.msk_sb = a->mask_stride_b;
+    p.B = a->B; p.Sk = a->Sk; p.H = a->H; p.k_splits = a->k_splits > 1 ? a->k_splits : 1;
+    p.scale = a->scale; p.out_acc = a->out_acc; p.lse_acc = a->lse_acc;
+    return launch(name, kernel, (long)p.B * p.k_splits, kDecThreads, kDecqLdsBytes<F>, stream, p);
 }
 
 }  // namespace lwm
@@ -204,180 +277,49 @@ int lwm_kv_cache_write_at(void* cache, const void* src, int32_t B, int64_t cache
                   cache_rows, src_row0, nrows, (int)row_elems);
 }
 
-static int kv8_write_params(const char* name, lwm::Kv8WriteParams* p, void* cache, const void* src, int32_t B,
-                            int64_t cache_stride_b, int64_t src_stride_b, int64_t src_row0, int64_t nrows,
-                            int32_t row_elems, float* scale, int64_t scale_stride_b, int32_t H) {
-    using namespace lwm;
-    if (!cache || !src || !scale) return fail(LWM_EINVAL, "%s: null pointer", name);
-    if (B < 0 || nrows < 0 || H <= 0 || src_row0 < 0 || cache_stride_b < 0 || scale_stride_b < 0 || src_stride_b < 0)
-        return fail(LWM_EINVAL, "%s: bad dimension", name);
-    if (row_elems != H * kHeadDim)
-        return fail(LWM_EUNSUPPORTED, "%s: row_elems = %ld, H * 128 = %ld (head_dim is 128)", name, (long)row_elems, (long)H * kHeadDim);
-    if (!aligned16(cache) || !aligned16(src) || (cache_stride_b & 15) || (src_stride_b & 7) || (((uintptr_t)scale) & 3))
-        return fail(LWM_EUNSUPPORTED, "%s: misaligned (cache and src rows 16-byte aligned, scale 4-byte)", name);
-    p->cache = (uint8_t*)cache; p->scale = scale; p->src = (const bf16_t*)src;
-    p->cache_sb = cache_stride_b; p->scale_sb = scale_stride_b; p->src_sb = src_stride_b;
-    p->row0_dev = nullptr; p->dst_row0 = 0; p->cache_rows = 0;
-    p->src_row0 = src_row0; p->nrows = nrows; p->B = B; p->H = H;
-    return 0;
-}
-
-static long kv8_write_blocks(const lwm::Kv8WriteParams& p) {
-    const int64_t blocks = ((int64_t)p.B * p.nrows * p.H * 16 + 255) / 256;
-    return (long)(blocks > 16384 ? 16384 : blocks);
-}
+static const char kKv8WriteAlign[] = "cache and src rows 16-byte aligned, scale 4-byte";
+static const char kKv4WriteAlign[] = "src rows 16-byte aligned, cache and scale rows 4-byte";
 
 int lwm_kv8_cache_write(void* cache, const void* src, int32_t B, int64_t cache_stride_b,
                         int64_t src_stride_b, int64_t dst_row0, int64_t src_row0, int64_t nrows,
                         int32_t row_elems, float* scale, int64_t scale_stride_b, int32_t H, void* stream) {
-    using namespace lwm;
-    Kv8WriteParams p;
-    int r;
-    if ((r = kv8_write_params("kv8_cache_write", &p, cache, src, B, cache_stride_b, src_stride_b, src_row0, nrows,
-                              row_elems, scale, scale_stride_b, H))) return r;
-    if (dst_row0 < 0) return fail(LWM_EINVAL, "%s", "kv8_cache_write: bad dimension");
-    if (B == 0 || nrows == 0) return LWM_OK;
-    p.dst_row0 = dst_row0;
-    p.cache_rows = dst_row0 + nrows;              // the caller has checked the range against its cache
-    return launch("kv8_quant_write", kv8_quant_write_kernel, kv8_write_blocks(p), 256, 0, stream, p);
+    return lwm::kvq_cache_write("kv8_cache_write", "kv8_quant_write", lwm::kv8_quant_write_kernel, false, LWM_EUNSUPPORTED, 16,
+                                           1, kKv8WriteAlign, cache, src, B, cache_stride_b, src_stride_b, nullptr, dst_row0, 0,
+                                           src_row0, nrows, row_elems, scale, scale_stride_b, H, stream);
 }
 
 int lwm_kv8_cache_write_at(void* cache, const void* src, int32_t B, int64_t cache_stride_b,
                            int64_t src_stride_b, const int32_t* dst_row0_dev, int64_t row_offset,
                            int64_t cache_rows, int64_t src_row0, int64_t nrows, int32_t row_elems,
                            float* scale, int64_t scale_stride_b, int32_t H, void* stream) {
-    using namespace lwm;
-    Kv8WriteParams p;
-    int r;
-    if ((r = kv8_write_params("kv8_cache_write_at", &p, cache, src, B, cache_stride_b, src_stride_b, src_row0, nrows,
-                              row_elems, scale, scale_stride_b, H))) return r;
-    if (!dst_row0_dev) return fail(LWM_EINVAL, "%s", "kv8_cache_write_at: null pointer");
-    if (cache_rows < 0) return fail(LWM_EINVAL, "%s", "kv8_cache_write_at: bad dimension");
-    if (B == 0 || nrows == 0) return LWM_OK;
-    p.row0_dev = dst_row0_dev;
-    p.dst_row0 = row_offset;
-    p.cache_rows = cache_rows;
-    return launch("kv8_quant_write_at", kv8_quant_write_at_kernel, kv8_write_blocks(p), 256, 0, stream, p);
-}
-
-int lwm_attn_decode_kv8(const LwmKv8DecodeArgs* a, void* stream) {
-    using namespace lwm;
-    if (!a) return fail(LWM_EINVAL, "%s", "attn_decode_kv8: args is null");
-    int r;
-    if ((r = check_t4("q", a->q, true))) return r;
-    if (a->D != kHeadDim) return fail(LWM_EUNSUPPORTED, "%s: head_dim %ld (only 128)", "attn_decode_kv8", a->D);
-    if (a->B < 0 || a->Sk < 0 || a->H <= 0) return fail(LWM_EINVAL, "%s", "attn_decode_kv8: bad dimension");
-    if (!(a->scale > 0.0f)) return fail(LWM_EINVAL, "%s", "attn_decode_kv8: scale must be > 0");
-    if (!a->k || !a->v || !a->k_scale || !a->v_scale || !a->out_acc || !a->lse_acc)
-        return fail(LWM_EINVAL, "%s", "attn_decode_kv8: null pointer (k, v, k_scale, v_scale, out_acc, lse_acc)");
-    if (!aligned16(a->k) || !aligned16(a->v) || !aligned16(a->out_acc) || ((a->k_stride_b | a->k_stride_s | a->k_stride_h |
-                                                                          a->v_stride_b | a->v_stride_s | a->v_stride_h) & 15))
-        return fail(LWM_EUNSUPPORTED, "%s", "attn_decode_kv8: cache rows and out_acc must be 16-byte aligned (pointers and strides)");
-    if ((((uintptr_t)a->k_scale | (uintptr_t)a->v_scale | (uintptr_t)a->lse_acc) & 3))
-        return fail(LWM_EUNSUPPORTED, "%s", "attn_decode_kv8: scales and lse_acc must be 4-byte aligned");
-    if (a->k_splits < 0 || a->k_splits > 4096) return fail(LWM_EINVAL, "%s", "attn_decode_kv8: k_splits out of range");
-    if (a->B == 0) return LWM_OK;
-    Kv8DecodeParams p;
-    p.q = (const bf16_t*)a->q.ptr; p.q_sb = a->q.stride_b; p.q_sh = a->q.stride_h;
-    p.k = (const uint8_t*)a->k; p.v = (const uint8_t*)a->v; p.k_scale = a->k_scale; p.v_scale = a->v_scale;
-    p.k_sb = a->k_stride_b; p.k_ss = a->k_stride_s; p.k_sh = a->k_stride_h;
-    p.v_sb = a->v_stride_b; p.v_ss = a->v_stride_s; p.v_sh = a->v_stride_h;
-    p.ks_sb = a->k_scale_stride_b; p.ks_ss = a->k_scale_stride_s;
-    p.vs_sb = a->v_scale_stride_b; p.vs_ss = a->v_scale_stride_s;
-    p.dense_mask = a->dense_mask; p.msk_sb = a->mask_stride_b;
-    p.B = a->B; p.Sk = a->Sk; p.H = a->H; p.k_splits = a->k_splits > 1 ? a->k_splits : 1;
-    p.scale = a->scale; p.out_acc = a->out_acc; p.lse_acc = a->lse_acc;
-    return launch("attn_decode_kv8", attn_decode_kv8_kernel, (long)p.B * p.k_splits, kDecThreads, kDec8LdsBytes, stream, p);
-}
-
-static int kv4_write_params(const char* name, lwm::Kv4WriteParams* p, void* cache, const void* src, int32_t B,
-                            int64_t cache_stride_b, int64_t src_stride_b, int64_t src_row0, int64_t nrows,
-                            int32_t row_elems, void* scale, int64_t scale_stride_b, int32_t H) {
-    using namespace lwm;
-    if (!cache || !src || !scale) return fail(LWM_EINVAL, "%s: null pointer", name);
-    if (B < 0 || nrows < 0 || H <= 0 || src_row0 < 0 || cache_stride_b < 0 || scale_stride_b < 0 || src_stride_b < 0)
-        return fail(LWM_EINVAL, "%s: bad dimension", name);
-    if (row_elems != H * kHeadDim)
-        return fail(LWM_EINVAL, "%s: row_elems = %ld, H * 128 = %ld (head_dim is 128)", name, (long)row_elems, (long)H * kHeadDim);
-    if (!aligned16(src) || (src_stride_b & 7) || (((uintptr_t)cache | (uintptr_t)cache_stride_b | (uintptr_t)scale_stride_b) & 3) ||
-        (((uintptr_t)scale) & 3))
-        return fail(LWM_EINVAL, "%s: misaligned (src rows 16-byte aligned, cache and scale rows 4-byte)", name);
-    p->cache = (uint8_t*)cache; p->scale = (uint8_t*)scale; p->src = (const bf16_t*)src;
-    p->cache_sb = cache_stride_b; p->scale_sb = scale_stride_b; p->src_sb = src_stride_b;
-    p->row0_dev = nullptr; p->dst_row0 = 0; p->cache_rows = 0;
-    p->src_row0 = src_row0; p->nrows = nrows; p->B = B; p->H = H;
-    return 0;
-}
-
-static long kv4_write_blocks(const lwm::Kv4WriteParams& p) {
-    const int64_t blocks = ((int64_t)p.B * p.nrows * p.H * 16 + 255) / 256;
-    return (long)(blocks > 16384 ? 16384 : blocks);
+    return lwm::kvq_cache_write("kv8_cache_write_at", "kv8_quant_write_at", lwm::kv8_quant_write_at_kernel, true, LWM_EUNSUPPORTED,
+                                           16, 1, kKv8WriteAlign, cache, src, B, cache_stride_b, src_stride_b, dst_row0_dev, row_offset,
+                                           cache_rows, src_row0, nrows, row_elems, scale, scale_stride_b, H, stream);
 }
 
 int lwm_kv4_cache_write(void* cache, const void* src, int32_t B, int64_t cache_stride_b,
                         int64_t src_stride_b, int64_t dst_row0, int64_t src_row0, int64_t nrows,
                         int32_t row_elems, void* scale, int64_t scale_stride_b, int32_t H, void* stream) {
-    using namespace lwm;
-    Kv4WriteParams p;
-    int r;
-    if ((r = kv4_write_params("kv4_cache_write", &p, cache, src, B, cache_stride_b, src_stride_b, src_row0, nrows,
-                              row_elems, scale, scale_stride_b, H))) return r;
-    if (dst_row0 < 0) return fail(LWM_EINVAL, "%s", "kv4_cache_write: bad dimension");
-    if (B == 0 || nrows == 0) return LWM_OK;
-    p.dst_row0 = dst_row0;
-    p.cache_rows = dst_row0 + nrows;              // the caller has checked the range against its cache
-    return launch("kv4_quant_write", kv4_quant_write_kernel, kv4_write_blocks(p), 256, 0, stream, p);
+    return lwm::kvq_cache_write("kv4_cache_write", "kv4_quant_write", lwm::kv4_quant_write_kernel, false, LWM_EINVAL, 4, 4,
+                                           kKv4WriteAlign, cache, src, B, cache_stride_b, src_stride_b, nullptr, dst_row0, 0, src_row0,
+                                           nrows, row_elems, scale, scale_stride_b, H, stream);
 }
 
 int lwm_kv4_cache_write_at(void* cache, const void* src, int32_t B, int64_t cache_stride_b,
                            int64_t src_stride_b, const int32_t* dst_row0_dev, int64_t row_offset,
                            int64_t cache_rows, int64_t src_row0, int64_t nrows, int32_t row_elems,
                            void* scale, int64_t scale_stride_b, int32_t H, void* stream) {
-    using namespace lwm;
-    Kv4WriteParams p;
-    int r;
-    if ((r = kv4_write_params("kv4_cache_write_at", &p, cache, src, B, cache_stride_b, src_stride_b, src_row0, nrows,
-                              row_elems, scale, scale_stride_b, H))) return r;
-    if (!dst_row0_dev) return fail(LWM_EINVAL, "%s", "kv4_cache_write_at: null pointer");
-    if (cache_rows < 0) return fail(LWM_EINVAL, "%s", "kv4_cache_write_at: bad dimension");
-    if (B == 0 || nrows == 0) return LWM_OK;
-    p.row0_dev = dst_row0_dev;
-    p.dst_row0 = row_offset;
-    p.cache_rows = cache_rows;
-    return launch("kv4_quant_write_at", kv4_quant_write_at_kernel, kv4_write_blocks(p), 256, 0, stream, p);
+    return lwm::kvq_cache_write("kv4_cache_write_at", "kv4_quant_write_at", lwm::kv4_quant_write_at_kernel, true, LWM_EINVAL, 4, 4,
+                                           kKv4WriteAlign, cache, src, B, cache_stride_b, src_stride_b, dst_row0_dev, row_offset,
+                                           cache_rows, src_row0, nrows, row_elems, scale, scale_stride_b, H, stream);
+}
+
+int lwm_attn_decode_kv8(const LwmKv8DecodeArgs* a, void* stream) {
+    return lwm::kvq_attn_decode<lwm::Kv8Format>("attn_decode_kv8", lwm::attn_decode_kv8_kernel, LWM_EUNSUPPORTED, 0, true, a, stream);
 }
 
 int lwm_attn_decode_kv4(const LwmKv4DecodeArgs* a, void* stream) {
-    using namespace lwm;
-    if (!a) return fail(LWM_EINVAL, "%s", "attn_decode_kv4: args is null");
-    int r;
-    if ((r = check_t4("q", a->q, true))) return r;
-    if (a->D != kHeadDim) return fail(LWM_EINVAL, "%s: head_dim %ld (only 128)", "attn_decode_kv4", a->D);
-    if (a->B < 0 || a->Sk < 0 || a->H <= 0) return fail(LWM_EINVAL, "%s", "attn_decode_kv4: bad dimension");
-    if (!(a->scale > 0.0f)) return fail(LWM_EINVAL, "%s", "attn_decode_kv4: scale must be > 0");
-    if (!a->k || !a->v || !a->k_scale || !a->v_scale || !a->out_acc || !a->lse_acc)
-        return fail(LWM_EINVAL, "%s", "attn_decode_kv4: null pointer (k, v, k_scale, v_scale, out_acc, lse_acc)");
-    if (!aligned16(a->k) || !aligned16(a->v) || !aligned16(a->out_acc) || ((a->k_stride_b | a->k_stride_s | a->k_stride_h |
-                                                                          a->v_stride_b | a->v_stride_s | a->v_stride_h) & 15))
-        return fail(LWM_EINVAL, "%s", "attn_decode_kv4: cache rows and out_acc must be 16-byte aligned (pointers and strides)");
-    if (a->k_stride_s < 0 || a->v_stride_s < 0 || a->k_stride_h < 64 || a->v_stride_h < 64 || a->k_scale_stride_s < 0 ||
-        a->v_scale_stride_s < 0 || a->k_scale_stride_b < 0 || a->v_scale_stride_b < 0 || a->k_stride_b < 0 || a->v_stride_b < 0)
-        return fail(LWM_EINVAL, "%s", "attn_decode_kv4: bad strides (non-negative; a head is 64 bytes)");
-    if (((uintptr_t)a->lse_acc) & 3) return fail(LWM_EINVAL, "%s", "attn_decode_kv4: lse_acc must be 4-byte aligned");
-    if (a->k_splits < 0 || a->k_splits > 4096) return fail(LWM_EINVAL, "%s", "attn_decode_kv4: k_splits out of range");
-    if (a->B == 0) return LWM_OK;
-    Kv4DecodeParams p;
-    p.q = (const bf16_t*)a->q.ptr; p.q_sb = a->q.stride_b; p.q_sh = a->q.stride_h;
-    p.k = (const uint8_t*)a->k; p.v = (const uint8_t*)a->v;
-    p.k_scale = (const uint8_t*)a->k_scale; p.v_scale = (const uint8_t*)a->v_scale;
-    p.k_sb = a->k_stride_b; p.k_ss = a->k_stride_s; p.k_sh = a->k_stride_h;
-    p.v_sb = a->v_stride_b; p.v_ss = a->v_stride_s; p.v_sh = a->v_stride_h;
-    p.ks_sb = a->k_scale_stride_b; p.ks_ss = a->k_scale_stride_s;
-    p.vs_sb = a->v_scale_stride_b; p.vs_ss = a->v_scale_stride_s;
-    p.dense_mask = a->dense_mask; p.msk_sb = a->mask_stride_b;
-    p.B = a->B; p.Sk = a->Sk; p.H = a->H; p.k_splits = a->k_splits > 1 ? a->k_splits : 1;
-    p.scale = a->scale; p.out_acc = a->out_acc; p.lse_acc = a->lse_acc;
-    return launch("attn_decode_kv4", attn_decode_kv4_kernel, (long)p.B * p.k_splits, kDecThreads, kDec4LdsBytes, stream, p);
+    return lwm::kvq_attn_decode<lwm::Kv4Format>("attn_decode_kv4", lwm::attn_decode_kv4_kernel, LWM_EINVAL, 64, false, a, stream);
 }
 
 int lwm_attn_prefill_kv8(const LwmKv8PrefillArgs* a, void* stream) {

@@ -29,72 +29,104 @@ LWM_DEVICE void unpack_bf16x8(u32x4 raw, float (&f)[8]) {
     }
 }
 
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// ---- primitives of the decode kernels and of the 8-bit weight and cache kernels (the shared vocabulary of
+// wave_ops.h is pinned to the counter profile)
+#ifdef LWM_EMU
+LWM_DEVICE f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return f32x2{fmaf(a[0], b[0], c[0]), fmaf(a[1], b[1], c[1])}; }
+LWM_DEVICE f32x2 mad2(f32x2 a, f32x2 b, f32x2 c) { return a * b + c; }
+LWM_DEVICE void global_store_b32(void* p, uint32_t v) { memcpy(p, &v, 4); }
+#else
+// v_pk_fma_f32: the register pairs a packed conversion leaves are its operands as they are
+LWM_DEVICE f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
+// a * b + c as hipcc contracts it where it is free to: one fma.  (The host emulation is built without contraction and
+// rounds the product.)  For sums of TWO products, where the compiler would choose which one to round.
+LWM_DEVICE f32x2 mad2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
+LWM_DEVICE void global_store_b32(void* p, uint32_t v) { *(uint32_t*)p = v; }
+#endif
+// The loads written above this point are ISSUED above it: the optimiser may neither sink one below it (into the branch
+// of its first use, behind a wait for everything outstanding) nor hoist later work between them.  No instruction.
+LWM_DEVICE void issue_fence() {
+    asm volatile("" ::: "memory");
+    sched_fence();
+}
+LWM_DEVICE float global_load_f32(const float* p) { return *p; }
+LWM_DEVICE uint8_t global_load_u8(const uint8_t* p) { return *p; }
+LWM_DEVICE void global_store_f32(float* p, float v) { *p = v; }
+
+// Visible key range.  The reference attends over the WHOLE cache under the mask (kv_len = max_length,
+// lwm/llama.py:571-614); the keys beyond cache_index (and padding at either end) are masked.  Every
+// workgroup scans the mask row -- 1 B per key, L2-resident, against 8 KiB of K/V per key -- finds
+// [first, last] visible, and the k_splits pieces partition THAT range instead of [0, Sk): a generation
+// that has filled 2K of a 32K cache moves 1/16 of the bytes and still spreads them over every
+// workgroup (a piece's keys are a serial chain of HBM round trips, so few long pieces are slow).
+// Holes inside the range are handled per key by the caller.  Nothing visible -> ka = kz = 0: every piece
+// writes (0, -inf).  Without a mask row the pieces partition [0, Sk).  Uses 8 bytes of LDS per wave at
+// `lds`, with one barrier between their write and their read and none after: a caller that writes those
+// bytes again synchronises first.
+LWM_DEVICE void decode_visible_range(const uint8_t* mrow, int Sk, int split, int nsplit, lds_t lds, int& ka, int& kz) {
+    const int tid = thread_idx();
+    const int per = (Sk + nsplit - 1) / nsplit;
+    ka = split * per;
+    kz = ka + per < Sk ? ka + per : Sk;
+    if (!mrow) return;
+    int first = 0x7fffffff, last = -1;
+    // 16 mask bytes per load where the row allows it (a byte-wise scan of a 131072-key row by all 512
+    // pieces cost ~100 us); lowest / highest nonzero byte of a word from its lowest / highest set bit
+    const int nvec = (((uintptr_t)mrow & 15) == 0) ? (Sk >> 4) : 0;
+    for (int i = tid; i < nvec; i += kDecThreads) {
+        const u32x4 w = global_load_b128(mrow + 16 * i);
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if (w[c] != 0u) {
+                const int lo = 16 * i + 4 * c + (__builtin_ctz(w[c]) >> 3);
+                const int hi = 16 * i + 4 * c + ((31 - __builtin_clz(w[c])) >> 3);
+                first = lo < first ? lo : first;
+                last = hi > last ? hi : last;
+            }
+    }
+    for (int j = 16 * nvec + tid; j < Sk; j += kDecThreads)
+        if (mrow[j] != 0) {
+            first = j < first ? j : first;
+            last = j > last ? j : last;
+        }
+    for (int msk = 1; msk < 64; msk <<= 1) {
+        const int of = shfl_xor_i(first, msk), ol = shfl_xor_i(last, msk);
+        first = of < first ? of : first;
+        last = ol > last ? ol : last;
+    }
+    if ((tid & 63) == 0) {
+        lds_write_i32(lds + (tid >> 6) * 8, first);
+        lds_write_i32(lds + (tid >> 6) * 8 + 4, last);
+    }
+    block_sync();
+    for (int w = 0; w < kDecThreads / 64; ++w) {
+        const int of = lds_read_i32(lds + w * 8), ol = lds_read_i32(lds + w * 8 + 4);
+        first = of < first ? of : first;
+        last = ol > last ? ol : last;
+    }
+    if (last < 0) {
+        ka = kz = 0;
+    } else {
+        const int nv = last - first + 1;
+        const int pv = (nv + nsplit - 1) / nsplit;
+        ka = first + split * pv;
+        kz = ka + pv < last + 1 ? ka + pv : last + 1;
+        if (ka > kz) ka = kz;
+    }
+}
+
 LWM_KERNEL(kDecThreads) void attn_decode_kernel(AttnParams p) {
     const int tid = thread_idx();
     const int grp = tid >> 4, li = tid & 15;       // 32 head slots per pass, 16 lanes each
     const int nsplit = p.k_splits > 1 ? p.k_splits : 1;
     const int b = block_idx_x() / nsplit, split = block_idx_x() % nsplit;
-    const int per = (p.Sk + nsplit - 1) / nsplit;
-    const int k0 = split * per;
-    const int k1 = k0 + per < p.Sk ? k0 + per : p.Sk;
     const float c = p.scale * kLog2e;
     const uint8_t* mrow = p.dense_mask ? p.dense_mask + (int64_t)b * p.msk_sb : nullptr;
 
-    // Visible key range.  The reference attends over the WHOLE cache under the mask (kv_len = max_length,
-    // lwm/llama.py:571-614); the keys beyond cache_index (and padding at either end) are masked.  Every
-    // workgroup scans the mask row -- 1 B per key, L2-resident, against 8 KiB of K/V per key -- finds
-    // [first, last] visible, and the k_splits pieces partition THAT range instead of [0, Sk): a generation
-    // that has filled 2K of a 32K cache moves 1/16 of the bytes and still spreads them over every
-    // workgroup (a piece's keys are a serial chain of HBM round trips, so few long pieces are slow).
-    // Holes inside the range are handled per key below.  Nothing visible -> every piece writes (0, -inf).
-    int ka = k0, kz = k1;
-    if (mrow) {
-        int first = 0x7fffffff, last = -1;
-        // 16 mask bytes per load where the row allows it (a byte-wise scan of a 131072-key row by all 512
-        // pieces cost ~100 us); lowest / highest nonzero byte of a word from its lowest / highest set bit
-        const int nvec = (((uintptr_t)mrow & 15) == 0) ? (p.Sk >> 4) : 0;
-        for (int i = tid; i < nvec; i += kDecThreads) {
-            const u32x4 w = global_load_b128(mrow + 16 * i);
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-                if (w[c] != 0u) {
-                    const int lo = 16 * i + 4 * c + (__builtin_ctz(w[c]) >> 3);
-                    const int hi = 16 * i + 4 * c + ((31 - __builtin_clz(w[c])) >> 3);
-                    first = lo < first ? lo : first;
-                    last = hi > last ? hi : last;
-                }
-        }
-        for (int j = 16 * nvec + tid; j < p.Sk; j += kDecThreads)
-            if (mrow[j] != 0) {
-                first = j < first ? j : first;
-                last = j > last ? j : last;
-            }
-        for (int msk = 1; msk < 64; msk <<= 1) {
-            const int of = shfl_xor_i(first, msk), ol = shfl_xor_i(last, msk);
-            first = of < first ? of : first;
-            last = ol > last ? ol : last;
-        }
-        const lds_t scan = dyn_lds();
-        if ((tid & 63) == 0) {
-            lds_write_i32(scan + (tid >> 6) * 8, first);
-            lds_write_i32(scan + (tid >> 6) * 8 + 4, last);
-        }
-        block_sync();
-        for (int w = 0; w < kDecThreads / 64; ++w) {
-            const int of = lds_read_i32(scan + w * 8), ol = lds_read_i32(scan + w * 8 + 4);
-            first = of < first ? of : first;
-            last = ol > last ? ol : last;
-        }
-        if (last < 0) {
-            ka = kz = 0;
-        } else {
-            const int nv = last - first + 1;
-            const int pv = (nv + nsplit - 1) / nsplit;
-            ka = first + split * pv;
-            kz = ka + pv < last + 1 ? ka + pv : last + 1;
-            if (ka > kz) ka = kz;
-        }
-    }
+    int ka, kz;
+    decode_visible_range(mrow, p.Sk, split, nsplit, dyn_lds(), ka, kz);
 
     for (int h0 = 0; h0 < p.H; h0 += 32) {
         const int h = h0 + grp;

@@ -1,6 +1,6 @@
 // attn_prefill_kv8.h -- attention of a BLOCK of queries over the 8-bit (e4m3) KV cache: chunked prefill, a follow-up
-// turn, a block appended to a live cache.  Requires wave_ops.h + attn_common.h + attn_fwd.h + attn_decode_kv8.h
-// (the format, cvt_e4m3x2_lo/hi, issue_fence).
+// turn, a block appended to a live cache.  Requires wave_ops.h + attn_common.h + attn_fwd.h + attn_decode.h
+// (f32x2, issue_fence, global_load_u8, global_load_f32) + attn_decode_kv8.h (the format, cvt_e4m3x2_lo/hi).
 //
 // The kernel is attn_fwd_body<true> (attn_fwd.h) in its split-K partials form -- 512 threads, 256 queries per workgroup,
 // 64-key LDS tiles, the same workgroup -> (q tile, head, batch, split) map, causal tile range and split walk, and

@@ -16,7 +16,7 @@ import os
 
 import torch
 
-from . import ops as _ops
+from . import kv4 as _kv4, ops as _ops
 from .llama_ops import (LLaMAMLP, RMSNorm, apply_rotary_emb, chunked_lm_head_loss, decode_rows_scope, dense, dense_fused,
                         dense_multi, fused_dense_ok, parse_decode_rows, precompute_freqs_cis, qkv_rope, rmsnorm_residual,
                         rows_x_ok, swiglu)
@@ -240,9 +240,9 @@ class LLaMAAttention(torch.nn.Module):
         B, Q = xq.shape[:2]
         ck, cv = cache["cached_key"], cache["cached_value"]
         if "key_scale" in cache:
-            return self._cached_kv8(xq, xk, xv, attention_mask, cache)
+            return self._cached_kvq(_ops.KV8, xq, xk, xv, attention_mask, cache)
         if "key_scale_e8m0" in cache:
-            return self._cached_kv4(xq, xk, xv, attention_mask, cache)
+            return self._cached_kvq(_kv4.KV4, xq, xk, xv, attention_mask, cache)
         if "index_dev" in cache:
             # hipGraph-capturable decode step: cache_index lives on the device (one int32 shared by all
             # layers), the mask was built from it once for this step, and the new row is written by
@@ -272,51 +272,50 @@ class LLaMAAttention(torch.nn.Module):
         cache["cache_index"] = concatenate_to_cache(ck, cv, xk.contiguous(), xv, idx, axis_name="sp")
         return ringattention_inference(xq.contiguous(), ck, cv, mask, axis_name="sp")
 
-    def _cached_kv8(self, xq, xk, xv, attention_mask, cache):
-        """_cached over an 8-bit cache (init_cache(kv_dtype="fp8"): e4m3 bytes + one scale per row and head,
-        csrc/attn_decode_kv8.h).  Prefill (cache_index == 0): the cached path attends over rows [0, Q) only -- rows past
-        Q are invisible -- so the block attends over its OWN bf16 keys and values under the same structured mask, and
-        the rows are quantised into the cache afterwards: the prompt's own attention sees unquantised keys.  A decode
-        step quantises its row, then streams the cache (lwm_attn_decode_kv8 + the split-K combine)."""
+    def _cached_kvq(self, f, xq, xk, xv, attention_mask, cache):
+        """_cached over a quantised cache of format f (init_cache(kv_dtype="fp8" / "fp4"): ops.KV8, kv4.KV4;
+        csrc/attn_decode_kv8.h, attn_decode_kv4.h).  Prefill (cache_index == 0): the cached path attends over rows [0, Q)
+        only -- rows past Q are invisible -- so the block attends over its OWN bf16 keys and values under the same
+        structured mask, and the rows are quantised into the cache afterwards: the prompt's own attention sees
+        unquantised keys.  A decode step quantises its row, then streams the cache (lwm_attn_decode_kv8 / _kv4 + the
+        split-K combine).  A block at cache_index > 0 is refused unless the format has a block kernel and the cache was
+        made for blocks."""
         from .ring import _pick_splits
         B, Q, H, D = xq.shape
-        ck, cv, ks, vs = cache["cached_key"], cache["cached_value"], cache["key_scale"], cache["value_scale"]
-        if xq.dtype != torch.bfloat16:
-            raise NotImplementedError("kv_dtype='fp8' with a float32 model: the 8-bit cache quantises bf16 rows and its "
-                                      "decode kernel takes a bf16 query (--dtype=bf16, or the default cache)")
-        if sp_size_rank("sp")[0] > 1:
-            raise NotImplementedError("kv_dtype='fp8' with sp > 1: the 8-bit cache is not sharded over the sequence ring "
-                                      "(one rank, or the default cache)")
+        ck, cv, ks, vs = cache["cached_key"], cache["cached_value"], cache[f.scale_keys[0]], cache[f.scale_keys[1]]
+        _kvq_refuse(f, xq.dtype, sp_size_rank("sp")[0], D)
         xq, xk, xv = xq.contiguous(), xk.contiguous(), xv.contiguous()
         max_len = ck.shape[1]
+        blocks = (f"kv_dtype={f.kv_dtype!r} with Q > 1 at cache_index > 0: the {f.bits} cache takes a prompt at cache_index 0 and "
+                  "one token per step after it" + ("" if f.block_kernel else f" (a block kernel over the {f.bits} cache is not built)"))
         if "index_dev" in cache:                   # hipGraph-capturable step: see _cached
             if Q != 1:
-                raise NotImplementedError("kv_dtype='fp8' with Q > 1 at cache_index > 0: the 8-bit cache takes a prompt at "
-                                          "cache_index 0 and one token per step after it")
-            _ops.kv8_cache_write_at(ck, ks, xk, cache["index_dev"])
-            _ops.kv8_cache_write_at(cv, vs, xv, cache["index_dev"])
+                raise NotImplementedError(blocks)
+            _ops._kvq_cache_write_at(f, ck, ks, xk, cache["index_dev"])
+            _ops._kvq_cache_write_at(f, cv, vs, xv, cache["index_dev"])
             mask = (cache["mask_dev"][:, 0] != 0).to(torch.uint8).contiguous()
         else:
             idx = int(cache["cache_index"])
             if idx == 0:
                 kvld = None if attention_mask is None else attention_mask[:, :Q]
                 out = ringattention_inference(xq, xk, xv, None, axis_name="sp", causal_offset=0, key_valid=kvld)
-                _ops.kv8_cache_write(ck, ks, xk, dst_row0=0)
-                _ops.kv8_cache_write(cv, vs, xv, dst_row0=0)
+                _ops._kvq_cache_write(f, ck, ks, xk, dst_row0=0)
+                _ops._kvq_cache_write(f, cv, vs, xv, dst_row0=0)
                 cache["cache_index"] = Q
                 return out
-            if Q != 1 and cache.get("kv8_blocks"):
+            if Q != 1 and not (f.block_kernel and cache.get("kv8_blocks")):
+                raise NotImplementedError(blocks)
+            _ops._kvq_cache_write(f, ck, ks, xk, dst_row0=idx)
+            _ops._kvq_cache_write(f, cv, vs, xv, dst_row0=idx)
+            cache["cache_index"] = n = idx + Q
+            if Q != 1:
                 # a block appended to a live cache (init_cache(chunked_prefill=True)): the decode step's rule -- quantise
                 # your own rows, then read the cache -- for Q rows at once: the same as feeding the tokens one at a time.
                 # lwm_attn_prefill_kv8 dequantises while it stages; no bf16 copy of the cache is made
                 from .kv8 import attn_prefill_kv8
-                _ops.kv8_cache_write(ck, ks, xk, dst_row0=idx)
-                _ops.kv8_cache_write(cv, vs, xv, dst_row0=idx)
-                n = idx + Q
                 kvld = None if attention_mask is None else (attention_mask[:, :n] != 0).to(torch.uint8)
                 o_parts, l_parts = attn_prefill_kv8(xq, ck[:, :n], ks[:, :n], cv[:, :n], vs[:, :n], q_start=idx,
                                                     k_splits=_pick_splits(B, Q, H, n), key_valid=kvld)
-                cache["cache_index"] = n
                 if o_parts.shape[0] == 1:
                     # one piece: the partial IS the normalised output, and attn_combine's merge of one piece is the
                     # identity followed by the rounding to bf16 (the same bits: tests/test_gpu_kv8_prefill.py) -- but a
@@ -324,62 +323,21 @@ class LLaMAAttention(torch.nn.Module):
                     # the cast kernel's HBM time (profiles/r10_kv8_prefill.md)
                     return _ops.cast_f32_to_bf16(o_parts[0])
                 return _ops.attn_combine(o_parts, l_parts, want_bf16=True)[0]
-            if Q != 1:
-                raise NotImplementedError("kv_dtype='fp8' with Q > 1 at cache_index > 0: the 8-bit cache takes a prompt at "
-                                          "cache_index 0 and one token per step after it")
-            _ops.kv8_cache_write(ck, ks, xk, dst_row0=idx)
-            _ops.kv8_cache_write(cv, vs, xv, dst_row0=idx)
-            cache["cache_index"] = idx + 1
             mask = cached_visibility(B, 1, max_len, idx, attention_mask, xq.device)[:, 0].to(torch.uint8).contiguous()
-        o_parts, l_parts = _ops.attn_decode_kv8(xq, ck, ks, cv, vs, k_splits=_pick_splits(B, 1, H, max_len), dense_mask=mask)
+        o_parts, l_parts = _ops._kvq_attn_decode(f, xq, ck, ks, cv, vs, k_splits=_pick_splits(B, 1, H, max_len), dense_mask=mask)
         return _ops.attn_combine(o_parts, l_parts, want_bf16=True)[0]
 
 
-    def _cached_kv4(self, xq, xk, xv, attention_mask, cache):
-        """_cached over a 4-bit cache (init_cache(kv_dtype="fp4"): e2m1 nibbles + one e8m0 byte per block of 32,
-        csrc/attn_decode_kv4.h), by the rules of _cached_kv8.  Prefill (cache_index == 0): the block attends over its OWN
-        bf16 keys and values under the same structured mask and is quantised into the cache afterwards.  A decode step
-        quantises its row, then streams the cache (lwm_attn_decode_kv4 + the split-K combine).  A block at
-        cache_index > 0 is refused: a block kernel over the 4-bit cache is not built."""
-        from .ring import _pick_splits
-        from . import kv4 as _kv4
-        B, Q, H, D = xq.shape
-        ck, cv, ks, vs = cache["cached_key"], cache["cached_value"], cache["key_scale_e8m0"], cache["value_scale_e8m0"]
-        if xq.dtype != torch.bfloat16:
-            raise NotImplementedError("kv_dtype='fp4' with a float32 model: the 4-bit cache quantises bf16 rows and its "
-                                      "decode kernel takes a bf16 query (--dtype=bf16, or the default cache)")
-        if sp_size_rank("sp")[0] > 1:
-            raise NotImplementedError("kv_dtype='fp4' with sp > 1: the 4-bit cache is not sharded over the sequence ring "
-                                      "(one rank, or the default cache)")
-        if D != 128:
-            raise NotImplementedError(f"kv_dtype='fp4': head_dim {D} (the 4-bit decode kernel is built for 128)")
-        xq, xk, xv = xq.contiguous(), xk.contiguous(), xv.contiguous()
-        max_len = ck.shape[1]
-        blocks = ("kv_dtype='fp4' with Q > 1 at cache_index > 0: the 4-bit cache takes a prompt at cache_index 0 and one "
-                  "token per step after it (a block kernel over the 4-bit cache is not built)")
-        if "index_dev" in cache:                   # hipGraph-capturable step: see _cached
-            if Q != 1:
-                raise NotImplementedError(blocks)
-            _kv4.kv4_cache_write_at(ck, ks, xk, cache["index_dev"])
-            _kv4.kv4_cache_write_at(cv, vs, xv, cache["index_dev"])
-            mask = (cache["mask_dev"][:, 0] != 0).to(torch.uint8).contiguous()
-        else:
-            idx = int(cache["cache_index"])
-            if idx == 0:
-                kvld = None if attention_mask is None else attention_mask[:, :Q]
-                out = ringattention_inference(xq, xk, xv, None, axis_name="sp", causal_offset=0, key_valid=kvld)
-                _kv4.kv4_cache_write(ck, ks, xk, dst_row0=0)
-                _kv4.kv4_cache_write(cv, vs, xv, dst_row0=0)
-                cache["cache_index"] = Q
-                return out
-            if Q != 1:
-                raise NotImplementedError(blocks)
-            _kv4.kv4_cache_write(ck, ks, xk, dst_row0=idx)
-            _kv4.kv4_cache_write(cv, vs, xv, dst_row0=idx)
-            cache["cache_index"] = idx + 1
-            mask = cached_visibility(B, 1, max_len, idx, attention_mask, xq.device)[:, 0].to(torch.uint8).contiguous()
-        o_parts, l_parts = _kv4.attn_decode_kv4(xq, ck, ks, cv, vs, k_splits=_pick_splits(B, 1, H, max_len), dense_mask=mask)
-        return _ops.attn_combine(o_parts, l_parts, want_bf16=True)[0]
+def _kvq_refuse(f, dtype, n_sp, D):
+    """what no quantised cache serves, by name (init_cache and every step check the same three things)"""
+    if dtype != torch.bfloat16:
+        raise NotImplementedError(f"kv_dtype={f.kv_dtype!r} with a float32 model: the {f.bits} cache quantises bf16 rows and its "
+                                  "decode kernel takes a bf16 query (--dtype=bf16, or the default cache)")
+    if n_sp > 1:
+        raise NotImplementedError(f"kv_dtype={f.kv_dtype!r} with sp > 1: the {f.bits} cache is not sharded over the sequence ring "
+                                  "(one rank, or the default cache)")
+    if D != 128:
+        raise NotImplementedError(f"kv_dtype={f.kv_dtype!r}: head_dim {D} (the {f.bits} decode kernel is built for 128)")
 
 
 class LLaMABlock(torch.nn.Module):
@@ -607,35 +565,17 @@ class LLaMAForCausalLM(torch.nn.Module):
             raise ValueError(f"max_length {max_length} is not divisible by the sp ring size {n_sp}")
         if kv_dtype not in (None, "fp8", "fp4"):
             raise ValueError(f"kv_dtype={kv_dtype!r}: None (the model's dtype), 'fp8' or 'fp4'")
-        if kv_dtype == "fp4":
-            if self.dtype != torch.bfloat16:
-                raise NotImplementedError("kv_dtype='fp4' with a float32 model: the 4-bit cache quantises bf16 rows and its "
-                                          "decode kernel takes a bf16 query (--dtype=bf16, or the default cache)")
-            if n_sp > 1:
-                raise NotImplementedError("kv_dtype='fp4' with sp > 1: the 4-bit cache is not sharded over the sequence ring "
-                                          "(one rank, or the default cache)")
-            if D != 128:
-                raise NotImplementedError(f"kv_dtype='fp4': head_dim {D} (the 4-bit decode kernel is built for 128)")
-            if chunked_prefill:
-                raise NotImplementedError("kv_dtype='fp4' with chunked prefill (chunked_prefill=True, prefill_chunk=N): a block "
-                                          "kernel over the 4-bit cache is not built; kv_dtype='fp8' takes blocks")
-            q = lambda: torch.zeros(batch_size, max_length, H, D // 2, dtype=torch.uint8, device=device)
-            sc = lambda: torch.full((batch_size, max_length, H, 4), 127, dtype=torch.uint8, device=device)
-            return [dict(cached_key=q(), cached_value=q(), key_scale_e8m0=sc(), value_scale_e8m0=sc(), cache_index=0)
-                    for _ in self.h]
-        if kv_dtype == "fp8":
-            if self.dtype != torch.bfloat16:
-                raise NotImplementedError("kv_dtype='fp8' with a float32 model: the 8-bit cache quantises bf16 rows and its "
-                                          "decode kernel takes a bf16 query (--dtype=bf16, or the default cache)")
-            if n_sp > 1:
-                raise NotImplementedError("kv_dtype='fp8' with sp > 1: the 8-bit cache is not sharded over the sequence ring "
-                                          "(one rank, or the default cache)")
-            if D != 128:
-                raise NotImplementedError(f"kv_dtype='fp8': head_dim {D} (the 8-bit decode kernel is built for 128)")
-            q = lambda: torch.zeros(batch_size, max_length, H, D, dtype=torch.uint8, device=device)
-            sc = lambda: torch.ones(batch_size, max_length, H, dtype=torch.float32, device=device)
+        if kv_dtype is not None:
+            f = _ops.KV8 if kv_dtype == "fp8" else _kv4.KV4
+            _kvq_refuse(f, self.dtype, n_sp, D)
+            if chunked_prefill and not f.block_kernel:
+                raise NotImplementedError(f"kv_dtype={f.kv_dtype!r} with chunked prefill (chunked_prefill=True, prefill_chunk=N): a "
+                                          f"block kernel over the {f.bits} cache is not built; kv_dtype='fp8' takes blocks")
+            q = lambda: torch.zeros(batch_size, max_length, H, f.head_bytes, dtype=torch.uint8, device=device)
+            sc = lambda: torch.full((batch_size, max_length, H) + f.scale_tail, f.scale_one, dtype=f.scale_dtype, device=device)
             mark = dict(kv8_blocks=True) if chunked_prefill else {}
-            return [dict(cached_key=q(), cached_value=q(), key_scale=sc(), value_scale=sc(), cache_index=0, **mark) for _ in self.h]
+            return [{"cached_key": q(), "cached_value": q(), f.scale_keys[0]: sc(), f.scale_keys[1]: sc(), "cache_index": 0, **mark}
+                    for _ in self.h]
         # sharded over "sp": each rank holds its contiguous max_length/sp rows (lwm/llama.py:454-467)
         z = lambda: torch.zeros(batch_size, max_length // n_sp, H, D, dtype=self.dtype, device=device)
         return [dict(cached_key=z(), cached_value=z(), cache_index=0) for _ in self.h]

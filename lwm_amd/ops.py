@@ -7,6 +7,7 @@ bf16/f32 on a ROCm device and the shared library must be present.
 import ctypes as C
 import os
 import math
+import typing
 
 import torch
 
@@ -271,74 +272,94 @@ def kv_cache_write_at(cache, src, index_dev, *, row_offset=0, src_row0=0, nrows=
     return cache
 
 
-def _kv8_check(cache, scale, src):
-    """(e4m3 bytes (B,S,H,128) u8, scales (B,S,H) f32, bf16 source (B,*,H,128)) with contiguous rows"""
+class KvFormat(typing.NamedTuple):
+    """What the front end knows of a quantised KV cache format (csrc/attn_decode_kvq.h; the formats themselves:
+    include/lwm_hip.h).  KV8 below, lwm_amd.kv4.KV4."""
+    name: str                   # "kv8": the prefix of the public names and of the error messages
+    kv_dtype: str               # "fp8": what init_cache / generate call it
+    bits: str                   # "8-bit"
+    codes: str                  # what the cache bytes are, in words
+    head_bytes: int             # bytes of one head (128 elements) of one cache row
+    scale_dtype: torch.dtype
+    scale_tail: tuple           # the scale tensors are (B, S, H) + scale_tail
+    scale_one: float            # the scale element that stands for 1 (an empty cache)
+    scale_keys: tuple           # the names of the two scale tensors in a model's cache dict
+    write: str                  # the three entry points
+    write_at: str
+    decode: str
+    decode_args: type
+    block_kernel: bool          # a block of queries over the cache (lwm_amd.kv8.attn_prefill_kv8)?
+
+
+KV8 = KvFormat("kv8", "fp8", "8-bit", "e4m3 bytes", 128, torch.float32, (), 1.0, ("key_scale", "value_scale"),
+               "lwm_kv8_cache_write", "lwm_kv8_cache_write_at", "lwm_attn_decode_kv8", _capi.LwmKv8DecodeArgs, True)
+
+
+def _kvq_check(f, cache, scale, src):
+    """(code bytes (B,S,H,head_bytes) u8, scales (B,S,H)+scale_tail, bf16 source (B,*,H,128)) with contiguous rows"""
+    hb = f.head_bytes
     if not cache.is_cuda or cache.dtype != torch.uint8 or cache.dim() != 4 or not cache[0].is_contiguous():
-        raise ValueError("cache: expected a uint8 (B,S,H,D) device tensor of e4m3 bytes with contiguous (S,H,D)")
-    B, rows, H, D = cache.shape
-    if not scale.is_cuda or scale.dtype != torch.float32 or tuple(scale.shape) != (B, rows, H) or not scale[0].is_contiguous():
-        raise ValueError(f"scale: expected an f32 device tensor of shape {(B, rows, H)} with contiguous (S,H)")
+        raise ValueError(f"cache: expected a uint8 (B,S,H,{hb}) device tensor of {f.codes} with contiguous (S,H,{hb})")
+    B, rows, H, last = cache.shape
+    if last != hb:
+        raise ValueError(f"cache: last dimension {last}; the {f.bits} cache holds heads of 128 elements in {hb} bytes")
+    sshape = (B, rows, H) + f.scale_tail
+    if not scale.is_cuda or scale.dtype != f.scale_dtype or tuple(scale.shape) != sshape or not scale[0].is_contiguous():
+        raise ValueError(f"scale: expected a {f.scale_dtype} device tensor of shape {sshape} with contiguous rows")
     if not src.is_cuda or src.dtype != torch.bfloat16 or src.dim() != 4 or not src[0].is_contiguous() or \
-            src.shape[0] != B or tuple(src.shape[2:]) != (H, D):
-        raise ValueError(f"src: expected a bf16 device tensor (B,*,H,D) = ({B},*,{H},{D}) with contiguous (S,H,D) "
-                         "(the 8-bit cache quantises bf16 rows; there is no float32 flavour)")
-    return B, rows, H, D
+            src.shape[0] != B or tuple(src.shape[2:]) != (H, 128):
+        raise ValueError(f"src: expected a bf16 device tensor (B,*,H,D) = ({B},*,{H},128) with contiguous (S,H,D) "
+                         f"(the {f.bits} cache quantises bf16 rows; there is no float32 flavour)")
+    return B, rows, H, 128
 
 
-def kv8_cache_write(cache, scale, src, *, dst_row0, src_row0=0, nrows=None):
-    """Quantise src[:, src_row0:src_row0+nrows] (bf16) into the 8-bit cache at row dst_row0: `cache` takes the e4m3fn
-    bytes, `scale` one power-of-two f32 per (row, head) (lwm_kv8_cache_write; the format: include/lwm_hip.h)."""
-    B, rows, H, D = _kv8_check(cache, scale, src)
+def _kvq_cache_write(f, cache, scale, src, *, dst_row0, src_row0=0, nrows=None):
+    B, rows, H, D = _kvq_check(f, cache, scale, src)
     if nrows is None:
         nrows = src.shape[1] - src_row0
     if dst_row0 < 0 or dst_row0 + nrows > rows or src_row0 < 0 or src_row0 + nrows > src.shape[1]:
-        raise ValueError("kv8_cache_write: row range out of bounds")
+        raise ValueError(f"{f.name}_cache_write: row range out of bounds")
     L = lib()
-    _capi.check(L, L.lwm_kv8_cache_write(cache.data_ptr(), src.data_ptr(), B, cache.stride(0), src.stride(0), dst_row0,
-                                         src_row0, nrows, H * D, scale.data_ptr(), scale.stride(0), H, _stream_ptr()),
-                "lwm_kv8_cache_write")
+    _capi.check(L, getattr(L, f.write)(cache.data_ptr(), src.data_ptr(), B, cache.stride(0), src.stride(0), dst_row0, src_row0,
+                                       nrows, H * D, scale.data_ptr(), scale.stride(0), H, _stream_ptr()), f.write)
     return cache, scale
 
 
-def kv8_cache_write_at(cache, scale, src, index_dev, *, row_offset=0, src_row0=0, nrows=None):
-    """The same with the destination row `index + row_offset` read from an int32 DEVICE tensor
-    (lwm_kv8_cache_write_at); rows that fall outside the cache are skipped."""
-    B, rows, H, D = _kv8_check(cache, scale, src)
+def _kvq_cache_write_at(f, cache, scale, src, index_dev, *, row_offset=0, src_row0=0, nrows=None):
+    B, rows, H, D = _kvq_check(f, cache, scale, src)
     if not index_dev.is_cuda or index_dev.dtype != torch.int32 or index_dev.numel() != 1:
         raise ValueError("index_dev: expected a one-element int32 device tensor")
     if nrows is None:
         nrows = src.shape[1] - src_row0
     if src_row0 < 0 or src_row0 + nrows > src.shape[1]:
-        raise ValueError("kv8_cache_write_at: source row range out of bounds")
+        raise ValueError(f"{f.name}_cache_write_at: source row range out of bounds")
     L = lib()
-    _capi.check(L, L.lwm_kv8_cache_write_at(cache.data_ptr(), src.data_ptr(), B, cache.stride(0), src.stride(0),
-                                            index_dev.data_ptr(), row_offset, rows, src_row0, nrows, H * D,
-                                            scale.data_ptr(), scale.stride(0), H, _stream_ptr()),
-                "lwm_kv8_cache_write_at")
+    _capi.check(L, getattr(L, f.write_at)(cache.data_ptr(), src.data_ptr(), B, cache.stride(0), src.stride(0),
+                                          index_dev.data_ptr(), row_offset, rows, src_row0, nrows, H * D, scale.data_ptr(),
+                                          scale.stride(0), H, _stream_ptr()), f.write_at)
     return cache, scale
 
 
-def kv8_dequant(q, scale):
-    """The numbers an 8-bit cache holds, as bf16: e4m3(q) * scale, exactly (4 significant bits times a power of two).
-    A torch expression for tests and debugging -- the decode kernel never materialises it."""
-    return (q.view(torch.float8_e4m3fn).float() * scale.unsqueeze(-1)).to(torch.bfloat16)
-
-
-def attn_decode_kv8(q, cached_key, key_scale, cached_value, value_scale, *, k_splits, dense_mask=None, scale=None):
-    """One query per batch row over the 8-bit cache (lwm_attn_decode_kv8): q bf16 (B,1,H,D); the cache as written by
-    kv8_cache_write; dense_mask u8 (B,1,Sk) or None.  Returns normalised partials (o_parts f32 [k_splits,B,1,H,D],
-    lse_parts f32 [k_splits,B,H,1]) -- merge with attn_combine."""
+def _kvq_attn_decode(f, q, cached_key, key_scale, cached_value, value_scale, *, k_splits, dense_mask=None, scale=None):
+    who = f"attn_decode_{f.name}"
+    if not torch.is_tensor(q) or q.dim() != 4:
+        raise ValueError(f"{who}: q: expected a bf16 (B,1,H,D) device tensor")
     B, Sq, H, D = q.shape
     if Sq != 1 or q.dtype != torch.bfloat16:
-        raise ValueError("attn_decode_kv8: expected a bf16 (B,1,H,D) query (the 8-bit cache serves one-token decode steps)")
-    a = _capi.LwmKv8DecodeArgs()
+        raise ValueError(f"{who}: expected a bf16 (B,1,H,D) query (the {f.bits} cache serves one-token decode steps)")
+    if D != 128:
+        raise ValueError(f"{who}: head_dim {D} (the {f.bits} decode kernel is built for 128)")
+    a = f.decode_args()
     a.q = _t4(q, "q", torch.bfloat16)
     Sk = cached_key.shape[1]
+    cshape, sshape = (B, Sk, H, f.head_bytes), (B, Sk, H) + f.scale_tail
+    sstride = (math.prod(f.scale_tail),) + (1,) * len(f.scale_tail)         # the scales of a head and the heads of a row contiguous
     for n, c, s in (("key", cached_key, key_scale), ("value", cached_value, value_scale)):
-        if not c.is_cuda or c.dtype != torch.uint8 or tuple(c.shape) != (B, Sk, H, D) or c.stride(3) != 1:
-            raise ValueError(f"cached_{n}: expected a uint8 device tensor of shape {(B, Sk, H, D)} with contiguous D")
-        if not s.is_cuda or s.dtype != torch.float32 or tuple(s.shape) != (B, Sk, H) or s.stride(2) != 1:
-            raise ValueError(f"{n}_scale: expected an f32 device tensor of shape {(B, Sk, H)} with contiguous heads")
+        if not c.is_cuda or c.device != q.device or c.dtype != torch.uint8 or tuple(c.shape) != cshape or c.stride(3) != 1:
+            raise ValueError(f"cached_{n}: expected a uint8 tensor of shape {cshape} on {q.device} with contiguous bytes")
+        if not s.is_cuda or s.device != q.device or s.dtype != f.scale_dtype or tuple(s.shape) != sshape or \
+                tuple(s.stride()[2:]) != sstride:
+            raise ValueError(f"{n}_scale: expected a {f.scale_dtype} tensor of shape {sshape} on {q.device} with contiguous heads")
     a.k, a.v = cached_key.data_ptr(), cached_value.data_ptr()
     a.k_stride_b, a.k_stride_s, a.k_stride_h = cached_key.stride()[:3]
     a.v_stride_b, a.v_stride_s, a.v_stride_h = cached_value.stride()[:3]
@@ -353,13 +374,41 @@ def attn_decode_kv8(q, cached_key, key_scale, cached_value, value_scale, *, k_sp
     a.B, a.Sk, a.H, a.D = B, Sk, H, D
     a.scale = float(scale) if scale is not None else 1.0 / math.sqrt(D)
     k_splits = max(1, int(k_splits))
+    if k_splits > 4096:
+        raise ValueError(f"{who}: k_splits = {k_splits} > 4096")
     a.k_splits = k_splits
     o_parts = torch.empty((k_splits, B, 1, H, D), dtype=torch.float32, device=q.device)
     lse_parts = torch.empty((k_splits, B, H, 1), dtype=torch.float32, device=q.device)
     a.out_acc, a.lse_acc = o_parts.data_ptr(), lse_parts.data_ptr()
     L = lib()
-    _capi.check(L, L.lwm_attn_decode_kv8(C.byref(a), _stream_ptr()), "lwm_attn_decode_kv8")
+    _capi.check(L, getattr(L, f.decode)(C.byref(a), _stream_ptr()), f.decode)
     return o_parts, lse_parts
+
+
+def kv8_cache_write(cache, scale, src, *, dst_row0, src_row0=0, nrows=None):
+    """Quantise src[:, src_row0:src_row0+nrows] (bf16) into the 8-bit cache at row dst_row0: `cache` takes the e4m3fn
+    bytes, `scale` one power-of-two f32 per (row, head) (lwm_kv8_cache_write; the format: include/lwm_hip.h)."""
+    return _kvq_cache_write(KV8, cache, scale, src, dst_row0=dst_row0, src_row0=src_row0, nrows=nrows)
+
+
+def kv8_cache_write_at(cache, scale, src, index_dev, *, row_offset=0, src_row0=0, nrows=None):
+    """The same with the destination row `index + row_offset` read from an int32 DEVICE tensor
+    (lwm_kv8_cache_write_at); rows that fall outside the cache are skipped."""
+    return _kvq_cache_write_at(KV8, cache, scale, src, index_dev, row_offset=row_offset, src_row0=src_row0, nrows=nrows)
+
+
+def kv8_dequant(q, scale):
+    """The numbers an 8-bit cache holds, as bf16: e4m3(q) * scale, exactly (4 significant bits times a power of two).
+    A torch expression for tests and debugging -- the decode kernel never materialises it."""
+    return (q.view(torch.float8_e4m3fn).float() * scale.unsqueeze(-1)).to(torch.bfloat16)
+
+
+def attn_decode_kv8(q, cached_key, key_scale, cached_value, value_scale, *, k_splits, dense_mask=None, scale=None):
+    """One query per batch row over the 8-bit cache (lwm_attn_decode_kv8): q bf16 (B,1,H,D); the cache as written by
+    kv8_cache_write; dense_mask u8 (B,1,Sk) or None.  Returns normalised partials (o_parts f32 [k_splits,B,1,H,D],
+    lse_parts f32 [k_splits,B,H,1]) -- merge with attn_combine."""
+    return _kvq_attn_decode(KV8, q, cached_key, key_scale, cached_value, value_scale, k_splits=k_splits, dense_mask=dense_mask,
+                            scale=scale)
 
 
 def bwd_stats_shape(B, H, Sq):

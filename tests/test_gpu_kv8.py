@@ -331,6 +331,14 @@ def test_refused_cases_are_named():
             model.init_cache(1, 32, kv_dtype="fp8")
     finally:
         M.sp_size_rank = orig
+    # the decode wrapper: a query that is not (B,1,H,D), more pieces than the entry takes
+    from lwm_amd import ops
+    q = torch.zeros(1, 1, 2, 128, dtype=torch.bfloat16, device="cuda")
+    kq, sc = torch.zeros(1, 8, 2, 128, dtype=torch.uint8, device="cuda"), torch.ones(1, 8, 2, device="cuda")
+    with pytest.raises(ValueError, match=r"attn_decode_kv8: q: expected a bf16 \(B,1,H,D\)"):
+        ops.attn_decode_kv8(q[0], kq, sc, kq, sc, k_splits=1)
+    with pytest.raises(ValueError, match="attn_decode_kv8: k_splits = 4097 > 4096"):
+        ops.attn_decode_kv8(q, kq, sc, kq, sc, k_splits=4097)
 
 
 # ---------------------------------------------------------------- what quantisation costs: the induction needle

@@ -178,7 +178,7 @@ def test_prefill_kv8_one_query_against_the_decode_kernel():
 
 
 def test_one_piece_cast_equals_the_combine():
-    """_cached_kv8 rounds a single piece with the cast kernel instead of merging it: the same bits"""
+    """_cached_kvq rounds a single piece with the cast kernel instead of merging it: the same bits"""
     import torch
     from lwm_amd import ops
     i = [c[5] for c in CASES].index(1)
