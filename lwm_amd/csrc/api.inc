@@ -688,22 +688,56 @@ int64_t lwm_gemv_workspace_bytes(int32_t rows, int32_t K, int32_t N) {
     return (int64_t)((K + lwm::kGemvKT - 1) / lwm::kGemvKT) * rows * N * (int64_t)sizeof(float);
 }
 
-int lwm_gemv_fused_bf16(const LwmGemvArgs* a, void* stream) {
-    using namespace lwm;
-    if (!a) return fail(LWM_EINVAL, "%s", "gemv: args is null");
+}  // extern "C"
+namespace lwm {
+// The four fused projection entries (gemv.h, gemv_w8.h, gemm_rows.h) share their checks, the K partition of GemvParams and
+// the launch pair with gemv_reduce_kernel.  What differs per entry is written down here.
+struct ProjEntry {
+    const char* tag;           // opens every text of lwm_last_error()
+    const char* kname;         // the streaming kernel, as launch() names it
+    int max_rows;
+    bool zero_rows_ok;         // no rows: LWM_OK and nothing is launched (else below the range)
+    int nt;                    // columns of W per workgroup
+    bool x16;                  // x and norm_weight are read 16 bytes at a time (else by the element)
+    bool one_res;              // a residual needs a single matrix (else it belongs to its matrix)
+    bool gemv_texts;           // the GEMV entries' wording of the range refusal, and their ss_out text with "%%" as they print it
+    bool names_scales;         // the null-matrix refusal names the scale table (the rows entries do in both formats)
+    int lds_fixed, lds_per_row;        // dynamic LDS of the streaming kernel: LDS per workgroup is occupancy, so not levelled
+};
+
+static const float* const* proj_scales(const LwmGemvArgs*) { return nullptr; }
+static const float* const* proj_scales(const LwmGemvW8Args* a) { return a->w_scale; }
+static const GemvParams& proj_params(void (*)(GemvParams), const GemvW8Params& pp) { return pp.g; }
+static const GemvW8Params& proj_params(void (*)(GemvW8Params), const GemvW8Params& pp) { return pp; }
+
+// A = LwmGemvArgs with a kernel over GemvParams, or LwmGemvW8Args with a kernel over GemvW8Params (scale tables exist).
+// The checks run in the order every entry has run them; the texts are format strings over the tag.
+template <class A, class P>
+static int proj_run(const ProjEntry& e, void (*kernel)(P), const A* a, void* stream) {
+    static_assert(kRowsThreads == kGemvThreads, "one workgroup size");
+    const char* who = e.tag;
+    if (!a) return fail(LWM_EINVAL, "%s: args is null", who);
+    const float* const* w_scale = proj_scales(a);
+    const bool w8 = w_scale != nullptr;
     const int32_t nmat = a->nmat, rows = a->rows, K = a->K;
-    if (!a->x || !a->workspace) return fail(LWM_EINVAL, "%s", "gemv: null pointer");
-    if (nmat < 1 || nmat > kGemvMaxMats) return fail(LWM_EINVAL, "%s", "gemv: 1..3 matrices per call");
-    if (rows < 0 || K <= 0) return fail(LWM_EINVAL, "%s", "gemv: bad dimension");
-    if (rows > kGemvMaxRows || (K & 31) || K > 8 * 12 * kGemvKT)
-        return fail(LWM_EUNSUPPORTED, "%s: rows=%ld K=%ld (need rows <= 4, K %% 32 == 0, K <= 12288)", "gemv", rows, K);
-    if (!aligned16(a->workspace) || a->ldx < K) return fail(LWM_EINVAL, "%s", "gemv: misaligned workspace or bad ldx");
-    if (a->norm_weight && (!a->ss_in || a->ss_n < 1 || a->ss_n > 64 || !(a->eps >= 0.0f)))
-        return fail(LWM_EINVAL, "%s", "gemv: norm_weight needs ss_in with 1..64 partials per row and eps >= 0");
+    if (!a->x || !a->workspace) return fail(LWM_EINVAL, "%s: null pointer", who);
+    if (nmat < 1 || nmat > kGemvMaxMats) return fail(LWM_EINVAL, "%s: 1..3 matrices per call", who);
+    if (rows < 0 || K <= 0) return fail(LWM_EINVAL, "%s: bad dimension", who);
+    if ((rows < 1 && !e.zero_rows_ok) || rows > e.max_rows || (K & 31) || K > 8 * 12 * kGemvKT)
+        return fail(LWM_EUNSUPPORTED, e.gemv_texts ? "%s: rows=%ld K=%ld (need rows <= 4, K %% 32 == 0, K <= 12288)"
+                                                   : "%s: rows=%ld K=%ld (need 1 <= rows <= 32, K %% 32 == 0, K <= 12288)", who, rows, K);
+    if (!aligned16(a->workspace) || a->ldx < K || (e.x16 && (!aligned16(a->x) || (a->ldx & 7))))
+        return fail(LWM_EINVAL, e.x16 ? "%s: misaligned workspace or x, or bad ldx (need ldx >= K, ldx %% 8 == 0)"
+                                      : "%s: misaligned workspace or bad ldx", who);
+    if (a->norm_weight && ((e.x16 && !aligned16(a->norm_weight)) || !a->ss_in || a->ss_n < 1 || a->ss_n > 64 || !(a->eps >= 0.0f)))
+        return fail(LWM_EINVAL, e.x16 ? "%s: norm_weight needs 16-byte alignment, ss_in with 1..64 partials per row and eps >= 0"
+                                      : "%s: norm_weight needs ss_in with 1..64 partials per row and eps >= 0", who);
     if (a->ss_out && (nmat != 1 || !a->y[0] || (a->N[0] % kGemvSsCols)))
-        return fail(LWM_EINVAL, "%s", "gemv: ss_out needs one matrix with a bf16 output and N %% 128 == 0");
-    GemvParams p;
-    memset(&p, 0, sizeof(p));
+        return fail(LWM_EINVAL, e.gemv_texts ? "%s: ss_out needs one matrix with a bf16 output and N %%%% 128 == 0"
+                                             : "%s: ss_out needs one matrix with a bf16 output and N %% 128 == 0", who);
+    GemvW8Params pp;
+    memset(&pp, 0, sizeof(pp));
+    GemvParams& p = pp.g;
     p.x = (const bf16_t*)a->x; p.part = (float*)a->workspace; p.ldx = a->ldx; p.R = rows; p.K = K; p.nmat = nmat;
     p.KS = (K + kGemvKT - 1) / kGemvKT;
     p.gamma = (const bf16_t*)a->norm_weight; p.ss_in = a->ss_in; p.ss_n = a->ss_n; p.eps = a->eps; p.ss_out = a->ss_out;
@@ -713,28 +747,46 @@ int lwm_gemv_fused_bf16(const LwmGemvArgs* a, void* stream) {
         const int32_t n = a->N[i];
         float* yf = a->y_f32[i];
         void* yb = a->y[i];
-        if (!a->w[i] || (!yb && !yf)) return fail(LWM_EINVAL, "%s", "gemv: null matrix or no output");
-        if (n <= 0 || (n & 7)) return fail(LWM_EUNSUPPORTED, "%s: N=%ld (need N %% 8 == 0)", "gemv", n);
-        if (!aligned16(a->w[i]) || (yf && !aligned16(yf)) || (yb && ((((uintptr_t)yb) & 7) || (a->ldy[i] & 3) || a->ldy[i] < n)))
-            return fail(LWM_EINVAL, "%s", "gemv: misaligned pointer or bad leading dimension");
-        if (a->residual[i] && (!yb || (((uintptr_t)a->residual[i]) & 7) || (a->ldres[i] & 3) || a->ldres[i] < n))
-            return fail(LWM_EINVAL, "%s", "gemv: a residual needs a bf16 output, 8-byte alignment and ldres >= N, a multiple of 4");
-        p.w[i] = (const bf16_t*)a->w[i]; p.y[i] = (bf16_t*)yb; p.y_f32[i] = yf; p.ldy[i] = yb ? a->ldy[i] : 0; p.N[i] = n;
+        if (!a->w[i] || (w8 && !w_scale[i]) || (!yb && !yf))
+            return fail(LWM_EINVAL, e.names_scales ? "%s: null matrix, null scale table or no output" : "%s: null matrix or no output", who);
+        if (n <= 0 || (n & 7)) return fail(LWM_EUNSUPPORTED, "%s: N=%ld (need N %% 8 == 0)", who, n);
+        if (!aligned16(a->w[i]) || (w8 && !aligned16(w_scale[i])) || (yf && !aligned16(yf)) ||
+            (yb && ((((uintptr_t)yb) & 7) || (a->ldy[i] & 3) || a->ldy[i] < n)))
+            return fail(LWM_EINVAL, "%s: misaligned pointer or bad leading dimension", who);
+        if (a->residual[i] && ((e.one_res && nmat != 1) || !yb || (((uintptr_t)a->residual[i]) & 7) || (a->ldres[i] & 3) || a->ldres[i] < n))
+            return fail(LWM_EINVAL, e.one_res ? "%s: a residual needs one matrix with a bf16 output, 8-byte alignment and ldres >= N, a multiple of 4"
+                                              : "%s: a residual needs a bf16 output, 8-byte alignment and ldres >= N, a multiple of 4", who);
+        if (w8) { pp.q[i] = (const uint8_t*)a->w[i]; pp.scale[i] = w_scale[i]; }
+        else p.w[i] = (const bf16_t*)a->w[i];
+        p.y[i] = (bf16_t*)yb; p.y_f32[i] = yf; p.ldy[i] = yb ? a->ldy[i] : 0; p.N[i] = n;
         p.res[i] = (const bf16_t*)a->residual[i]; p.ldres[i] = a->ldres[i];
         p.part_off[i] = off;
         off += (int64_t)p.KS * rows * n;
         p.blk0[i] = (int32_t)grid;
         p.quad0[i] = (int32_t)quads;
-        grid += (long)p.KS * ((n + kGemvNT - 1) / kGemvNT);
+        grid += (long)p.KS * ((n + e.nt - 1) / e.nt);
         quads += (long)rows * (n >> 2);
     }
     p.blk0[nmat] = (int32_t)grid;
     p.quad0[nmat] = (int32_t)quads;
     if (rows == 0) return LWM_OK;
-    int r = launch("gemv_bf16", gemv_bf16_kernel, grid, kGemvThreads, 3 * kGemvMaxRows * kGemvNT * 4, stream, p);
+    int r = launch(e.kname, kernel, grid, kGemvThreads, (size_t)(e.lds_fixed + rows * e.lds_per_row), stream, proj_params(kernel, pp));
     if (r) return r;
     return launch("gemv_reduce", gemv_reduce_kernel, (quads * 8 + 255) / 256, 256, 64, stream, p);
 }
+
+static const ProjEntry kProjGemv = {"gemv", "gemv_bf16", kGemvMaxRows, true, kGemvNT, false, false, true, false,
+                                    3 * kGemvMaxRows * kGemvNT * 4, 0};
+static const ProjEntry kProjGemvW8 = {"gemv_w8", "gemv_w8", kGemvMaxRows, true, kGemvW8NT, false, false, true, true,
+                                      0, 3 * kGemvW8NT * 4};
+static const ProjEntry kProjRows = {"gemm_rows", "gemm_rows_bf16", kRowsMax, false, kRowsNT, true, true, false, true,
+                                    kRowsLdsBytes, 0};
+static const ProjEntry kProjRowsW8 = {"gemm_rows_w8", "gemm_rows_w8", kRowsMax, false, kRowsNT, true, true, false, true,
+                                      kRowsLdsBytes, 0};
+}  // namespace lwm
+extern "C" {
+
+int lwm_gemv_fused_bf16(const LwmGemvArgs* a, void* stream) { return lwm::proj_run(lwm::kProjGemv, lwm::gemv_bf16_kernel, a, stream); }
 
 int lwm_gemv_multi_bf16(const void* x, int64_t ldx, int32_t nmat, const void* const* w, void* const* y, const int64_t* ldy,
                         float* const* y_f32, const int32_t* N, void* workspace, int32_t rows, int32_t K, void* stream) {
@@ -774,126 +826,14 @@ int lwm_w8_quantise(const void* w, void* q, float* scale, void* rounded, int32_t
     return launch("w8_quantise", w8_quantise_kernel, grid, 256, 4 * 64 * 32, stream, p);
 }
 
-int lwm_gemv_fused_w8(const LwmGemvW8Args* a, void* stream) {
-    using namespace lwm;
-    if (!a) return fail(LWM_EINVAL, "%s", "gemv_w8: args is null");
-    const int32_t nmat = a->nmat, rows = a->rows, K = a->K;
-    if (!a->x || !a->workspace) return fail(LWM_EINVAL, "%s", "gemv_w8: null pointer");
-    if (nmat < 1 || nmat > kGemvMaxMats) return fail(LWM_EINVAL, "%s", "gemv_w8: 1..3 matrices per call");
-    if (rows < 0 || K <= 0) return fail(LWM_EINVAL, "%s", "gemv_w8: bad dimension");
-    if (rows > kGemvMaxRows || (K & 31) || K > 8 * 12 * kGemvKT)
-        return fail(LWM_EUNSUPPORTED, "%s: rows=%ld K=%ld (need rows <= 4, K %% 32 == 0, K <= 12288)", "gemv_w8", rows, K);
-    if (!aligned16(a->workspace) || a->ldx < K) return fail(LWM_EINVAL, "%s", "gemv_w8: misaligned workspace or bad ldx");
-    if (a->norm_weight && (!a->ss_in || a->ss_n < 1 || a->ss_n > 64 || !(a->eps >= 0.0f)))
-        return fail(LWM_EINVAL, "%s", "gemv_w8: norm_weight needs ss_in with 1..64 partials per row and eps >= 0");
-    if (a->ss_out && (nmat != 1 || !a->y[0] || (a->N[0] % kGemvSsCols)))
-        return fail(LWM_EINVAL, "%s", "gemv_w8: ss_out needs one matrix with a bf16 output and N %% 128 == 0");
-    GemvW8Params pp;
-    memset(&pp, 0, sizeof(pp));
-    GemvParams& p = pp.g;
-    p.x = (const bf16_t*)a->x; p.part = (float*)a->workspace; p.ldx = a->ldx; p.R = rows; p.K = K; p.nmat = nmat;
-    p.KS = (K + kGemvKT - 1) / kGemvKT;
-    p.gamma = (const bf16_t*)a->norm_weight; p.ss_in = a->ss_in; p.ss_n = a->ss_n; p.eps = a->eps; p.ss_out = a->ss_out;
-    int64_t off = 0;
-    long grid = 0, quads = 0;
-    for (int i = 0; i < nmat; ++i) {
-        const int32_t n = a->N[i];
-        float* yf = a->y_f32[i];
-        void* yb = a->y[i];
-        if (!a->w[i] || !a->w_scale[i] || (!yb && !yf)) return fail(LWM_EINVAL, "%s", "gemv_w8: null matrix, null scale table or no output");
-        if (n <= 0 || (n % kGemvW8CPL)) return fail(LWM_EUNSUPPORTED, "%s: N=%ld (need N %% 8 == 0)", "gemv_w8", n);
-        if (!aligned16(a->w[i]) || !aligned16(a->w_scale[i]) || (yf && !aligned16(yf)) ||
-            (yb && ((((uintptr_t)yb) & 7) || (a->ldy[i] & 3) || a->ldy[i] < n)))
-            return fail(LWM_EINVAL, "%s", "gemv_w8: misaligned pointer or bad leading dimension");
-        if (a->residual[i] && (!yb || (((uintptr_t)a->residual[i]) & 7) || (a->ldres[i] & 3) || a->ldres[i] < n))
-            return fail(LWM_EINVAL, "%s", "gemv_w8: a residual needs a bf16 output, 8-byte alignment and ldres >= N, a multiple of 4");
-        pp.q[i] = (const uint8_t*)a->w[i]; pp.scale[i] = a->w_scale[i];
-        p.y[i] = (bf16_t*)yb; p.y_f32[i] = yf; p.ldy[i] = yb ? a->ldy[i] : 0; p.N[i] = n;
-        p.res[i] = (const bf16_t*)a->residual[i]; p.ldres[i] = a->ldres[i];
-        p.part_off[i] = off;
-        off += (int64_t)p.KS * rows * n;
-        p.blk0[i] = (int32_t)grid;
-        p.quad0[i] = (int32_t)quads;
-        grid += (long)p.KS * ((n + kGemvW8NT - 1) / kGemvW8NT);
-        quads += (long)rows * (n >> 2);
-    }
-    p.blk0[nmat] = (int32_t)grid;
-    p.quad0[nmat] = (int32_t)quads;
-    if (rows == 0) return LWM_OK;
-    int r = launch("gemv_w8", gemv_w8_kernel, grid, kGemvThreads, 3 * rows * kGemvW8NT * 4, stream, pp);
-    if (r) return r;
-    return launch("gemv_reduce", gemv_reduce_kernel, (quads * 8 + 255) / 256, 256, 64, stream, p);
-}
+int lwm_gemv_fused_w8(const LwmGemvW8Args* a, void* stream) { return lwm::proj_run(lwm::kProjGemvW8, lwm::gemv_w8_kernel, a, stream); }
 
-// ------------------------------------------------------------------ 1..32 rows on the matrix pipe (gemm_rows.h)
-}  // extern "C"
-namespace lwm {
-// the checks and the launch pair of both entries: A = LwmGemvArgs (scales null) or LwmGemvW8Args
-template <class A>
-static int gemm_rows_run(const A* a, const float* const* w_scale, const char* who, void* stream) {
-    const bool w8 = w_scale != nullptr;
-    if (!a) return fail(LWM_EINVAL, "%s: args is null", who);
-    const int32_t nmat = a->nmat, rows = a->rows, K = a->K;
-    if (!a->x || !a->workspace) return fail(LWM_EINVAL, "%s: null pointer", who);
-    if (nmat < 1 || nmat > kGemvMaxMats) return fail(LWM_EINVAL, "%s: 1..3 matrices per call", who);
-    if (rows < 0 || K <= 0) return fail(LWM_EINVAL, "%s: bad dimension", who);
-    if (rows < 1 || rows > kRowsMax || (K & 31) || K > 8 * 12 * kGemvKT)
-        return fail(LWM_EUNSUPPORTED, "%s: rows=%ld K=%ld (need 1 <= rows <= 32, K %% 32 == 0, K <= 12288)", who, rows, K);
-    if (!aligned16(a->workspace) || !aligned16(a->x) || a->ldx < K || (a->ldx & 7))
-        return fail(LWM_EINVAL, "%s: misaligned workspace or x, or bad ldx (need ldx >= K, ldx %% 8 == 0)", who);
-    if (a->norm_weight && (!aligned16(a->norm_weight) || !a->ss_in || a->ss_n < 1 || a->ss_n > 64 || !(a->eps >= 0.0f)))
-        return fail(LWM_EINVAL, "%s: norm_weight needs 16-byte alignment, ss_in with 1..64 partials per row and eps >= 0", who);
-    if (a->ss_out && (nmat != 1 || !a->y[0] || (a->N[0] % kGemvSsCols)))
-        return fail(LWM_EINVAL, "%s: ss_out needs one matrix with a bf16 output and N %% 128 == 0", who);
-    GemvW8Params pp;
-    memset(&pp, 0, sizeof(pp));
-    GemvParams& p = pp.g;
-    p.x = (const bf16_t*)a->x; p.part = (float*)a->workspace; p.ldx = a->ldx; p.R = rows; p.K = K; p.nmat = nmat;
-    p.KS = (K + kGemvKT - 1) / kGemvKT;
-    p.gamma = (const bf16_t*)a->norm_weight; p.ss_in = a->ss_in; p.ss_n = a->ss_n; p.eps = a->eps; p.ss_out = a->ss_out;
-    int64_t off = 0;
-    long grid = 0, quads = 0;
-    for (int i = 0; i < nmat; ++i) {
-        const int32_t n = a->N[i];
-        float* yf = a->y_f32[i];
-        void* yb = a->y[i];
-        if (!a->w[i] || (w8 && !w_scale[i]) || (!yb && !yf)) return fail(LWM_EINVAL, "%s: null matrix, null scale table or no output", who);
-        if (n <= 0 || (n & 7)) return fail(LWM_EUNSUPPORTED, "%s: N=%ld (need N %% 8 == 0)", who, n);
-        if (!aligned16(a->w[i]) || (w8 && !aligned16(w_scale[i])) || (yf && !aligned16(yf)) ||
-            (yb && ((((uintptr_t)yb) & 7) || (a->ldy[i] & 3) || a->ldy[i] < n)))
-            return fail(LWM_EINVAL, "%s: misaligned pointer or bad leading dimension", who);
-        if (a->residual[i] && (nmat != 1 || !yb || (((uintptr_t)a->residual[i]) & 7) || (a->ldres[i] & 3) || a->ldres[i] < n))
-            return fail(LWM_EINVAL, "%s: a residual needs one matrix with a bf16 output, 8-byte alignment and ldres >= N, a multiple of 4", who);
-        if (w8) { pp.q[i] = (const uint8_t*)a->w[i]; pp.scale[i] = w_scale[i]; }
-        else p.w[i] = (const bf16_t*)a->w[i];
-        p.y[i] = (bf16_t*)yb; p.y_f32[i] = yf; p.ldy[i] = yb ? a->ldy[i] : 0; p.N[i] = n;
-        p.res[i] = (const bf16_t*)a->residual[i]; p.ldres[i] = a->ldres[i];
-        p.part_off[i] = off;
-        off += (int64_t)p.KS * rows * n;
-        p.blk0[i] = (int32_t)grid;
-        p.quad0[i] = (int32_t)quads;
-        grid += (long)p.KS * ((n + kRowsNT - 1) / kRowsNT);
-        quads += (long)rows * (n >> 2);
-    }
-    p.blk0[nmat] = (int32_t)grid;
-    p.quad0[nmat] = (int32_t)quads;
-    int r = w8 ? launch("gemm_rows_w8", gemm_rows_w8_kernel, grid, kRowsThreads, kRowsLdsBytes, stream, pp)
-               : launch("gemm_rows_bf16", gemm_rows_bf16_kernel, grid, kRowsThreads, kRowsLdsBytes, stream, p);
-    if (r) return r;
-    return launch("gemv_reduce", gemv_reduce_kernel, (quads * 8 + 255) / 256, 256, 64, stream, p);
-}
-}  // namespace lwm
-extern "C" {
-
+// 1..32 rows on the matrix pipe (gemm_rows.h)
 int64_t lwm_gemm_rows_workspace_bytes(int32_t rows, int32_t K, int32_t N) { return lwm_gemv_workspace_bytes(rows, K, N); }
 
-int lwm_gemm_rows_fused_bf16(const LwmGemvArgs* a, void* stream) {
-    return lwm::gemm_rows_run(a, (const float* const*)nullptr, "gemm_rows", stream);
-}
+int lwm_gemm_rows_fused_bf16(const LwmGemvArgs* a, void* stream) { return lwm::proj_run(lwm::kProjRows, lwm::gemm_rows_bf16_kernel, a, stream); }
 
-int lwm_gemm_rows_fused_w8(const LwmGemvW8Args* a, void* stream) {
-    return lwm::gemm_rows_run(a, a ? a->w_scale : (const float* const*)nullptr, "gemm_rows_w8", stream);
-}
+int lwm_gemm_rows_fused_w8(const LwmGemvW8Args* a, void* stream) { return lwm::proj_run(lwm::kProjRowsW8, lwm::gemm_rows_w8_kernel, a, stream); }
 
 int lwm_softmax_ce_bf16(const void* logits, const int32_t* target, const float* weight, float* nll,
                         int32_t* correct, void* dlogits, int64_t rows, int32_t V, void* stream) {

@@ -22,8 +22,9 @@
 //     the swizzle sends the eight rows to eight different 32-byte bank groups -- conflict-free; a ds_write_b128 lane
 //     group (16 lanes) writes two whole rows;
 //   * the x fragment (batch row = lane % 16, 8 consecutive k) is one 16-byte global load per lane, no LDS;
-//   * RMSNorm on load: gemv_body's expression and its 64-lane tree over ss_in, per row -- the normalised x is bit for bit
-//     what lwm_gemv_fused_bf16 feeds its FMAs;
+//   * RMSNorm on load: gemv.h's gemv_norm expression and gemv_row_rstd tree over ss_in, per row, RESTATED here (as is
+//     gemv_tile's lookup) -- the normalised x is bit for bit what lwm_gemv_fused_bf16 feeds its FMAs.  Calling the shared
+//     functions gave the same bits and registers but cost the 32-row tile 1-3 % with the norm on (profiles/r16_proj_refactor.md);
 //   * 8-bit packs (gemv_w8.h's format): the bytes become bf16 on their way into LDS (an e4m3 value is exact in bf16), the
 //     group's power-of-two scale multiplies the finished partial once; everything between is the bf16 kernel's
 //     instruction stream.
@@ -96,7 +97,7 @@ LWM_DEVICE void gemm_rows_body(const GemvParams& p, const uint8_t* const* q, con
     float rstd[RB];
     for (int rb = 0; rb < RB; ++rb) rstd[rb] = 0.0f;
     if (p.gamma) {
-        // rstd of every row from its partials: gemv_body's tree (all 64 lanes end with the same sum), one row at a time
+        // rstd of every row from its partials: gemv_row_rstd's tree (all 64 lanes end with the same sum), one row at a time
         for (int r = 0; r < p.R; ++r) {
             float t = lane < p.ss_n ? p.ss_in[(int64_t)r * p.ss_n + lane] : 0.0f;
             for (int m = 1; m < 64; m <<= 1) t += shfl_xor_f(t, m);

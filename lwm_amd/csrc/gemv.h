@@ -19,6 +19,11 @@
 //       - RESIDUAL ADD in the reduction: y = bf16(bf16(x . W) + residual), the bf16 add the block would launch next
 //         (lwm/llama.py:719, :737), and the partial sums of squares of y for the next norm (ss_out).
 // R <= 4 rows, N % 8 == 0, K % 32 == 0, K <= 12288 (LWM-7B: 4096, 11008, 32000 all qualify).
+//
+// Shared with the other weight-streaming kernels: gemv_body<W, R> is the body of gemv_w8.h's kernel too (W = the weight
+// format: GemvBf16Format here, GemvW8Format there).  gemm_rows.h restates the tile lookup (gemv_tile) and the RMSNorm on
+// load (gemv_row_rstd, gemv_norm) inside its MFMA body and must stay equal to them; all three kernels feed
+// gemv_reduce_kernel the same partials layout.
 #pragma once
 
 namespace lwm {
@@ -55,21 +60,71 @@ constexpr int kGemvSsCols = 128;      // output columns per reduce workgroup = p
 LWM_DEVICE float bf16_lo(uint32_t u) { return __builtin_bit_cast(float, u << 16); }
 LWM_DEVICE float bf16_hi(uint32_t u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
 
-template <int R>
-LWM_DEVICE void gemv_body(const GemvParams& p) {
+// ---- the prologue of the streaming kernels (this header's and gemv_w8.h's; gemm_rows.h restates it)
+// the tile of a workgroup: matrix mi (uniform), its N, the K group ks of kGemvKT rows, the column block nb of `nt` columns
+struct GemvTile { int mi, N, ks, nb; };
+LWM_DEVICE GemvTile gemv_tile(const GemvParams& p, int nt) {
+    int mi = 0;
+    for (int i = 1; i < p.nmat; ++i) mi = block_idx_x() >= p.blk0[i] ? i : mi;
+    const int N = p.N[mi];
+    const int nbn = (N + nt - 1) / nt;
+    const int bl = block_idx_x() - p.blk0[mi];
+    return {mi, N, bl / nbn, bl % nbn};
+}
+
+// rstd of row r from its partials (every wave sums the same <= 64 numbers along the same tree: all 64 lanes end with the sum)
+LWM_DEVICE float gemv_row_rstd(const GemvParams& p, int r, int lane) {
+    float t = lane < p.ss_n ? p.ss_in[(int64_t)r * p.ss_n + lane] : 0.0f;
+    for (int m = 1; m < 64; m <<= 1) t += shfl_xor_f(t, m);
+    return 1.0f / sqrtf(t / (float)p.K + p.eps);
+}
+
+// RMSNorm on load: the arithmetic of rmsnorm_fwd_kernel
+LWM_DEVICE float gemv_norm(float x, float rstd, float g) { return (float)(bf16_t)((float)(bf16_t)(x * rstd) * g); }
+
+// The bf16 weight format of gemv_body (the e4m3 one: GemvW8Format in gemv_w8.h).  A format names the kernel's parameters,
+// one lane's load of 8 columns of a row, its accumulators for them and the FMA step of one row of W against x[r, i] of every row r, a scalar out of xv; quad(acc, j) gives
+// columns 4j..4j+3 of the accumulators.  kScaled: scale() loads the K group's scales of columns 4j..4j+3.
+struct GemvBf16Format {
+    using Params = GemvParams;
+    using Elem = bf16_t;
+    using Load = u32x4;
+    using Acc = float[8];
+    static constexpr bool kScaled = false;
+    LWM_DEVICE static const GemvParams& g(const Params& p) { return p; }
+    LWM_DEVICE static const Elem* matrix(const Params& p, int mi) { return p.w[mi]; }
+    LWM_DEVICE static Load load(const Elem* at) { return global_load_b128(at); }
+    LWM_DEVICE static void zero(Acc& a) {
+        for (int j = 0; j < 8; ++j) a[j] = 0.0f;
+    }
+    template <int R>
+    LWM_DEVICE static void fma(Acc (&a)[R], const Load& w, const float (&xv)[R], int i) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const float xs = lane_value(xv[r], i);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                a[r][2 * c] = fmaf(xs, bf16_lo(w[c]), a[r][2 * c]);
+                a[r][2 * c + 1] = fmaf(xs, bf16_hi(w[c]), a[r][2 * c + 1]);
+            }
+        }
+    }
+    LWM_DEVICE static f32x4 quad(const Acc& a, int j) { return f32x4{a[4 * j], a[4 * j + 1], a[4 * j + 2], a[4 * j + 3]}; }
+};
+
+// dynamic LDS: 3 * R * kGemvNT * 4 bytes are used
+template <class W, int R>
+LWM_DEVICE void gemv_body(const typename W::Params& pp) {
+    const GemvParams& p = W::g(pp);
     const lds_t lds = dyn_lds();
     const int tid = thread_idx();
     const int wave = wave_uniform(tid >> 6), lane = tid & 63;
-    int mi = 0;                                    // which matrix this workgroup belongs to (uniform)
-    for (int i = 1; i < p.nmat; ++i) mi = block_idx_x() >= p.blk0[i] ? i : mi;
-    const int N = p.N[mi];
-    const int nbn = (N + kGemvNT - 1) / kGemvNT;
-    const int bl = block_idx_x() - p.blk0[mi];
-    const int ks = bl / nbn, nb = bl % nbn;
+    const GemvTile t = gemv_tile(p, kGemvNT);
+    const int mi = t.mi, N = t.N, ks = t.ks;
     const int k0 = ks * kGemvKT + wave * kGemvRPW;
-    int n = nb * kGemvNT + lane * 8;
+    int n = t.nb * kGemvNT + lane * 8;
     const bool n_ok = n < N;
-    n = n_ok ? n : N - 8;                          // (clamped: the loads stay inside the matrix)
+    n = n_ok ? n : N - 8;                          // (clamped: the loads stay inside the matrix and the scale table)
     // this wave's 32 x values per row r, one per lane (lanes 32..63 repeat)
     float xv[R];
     for (int r = 0; r < R; ++r) {
@@ -77,72 +132,58 @@ LWM_DEVICE void gemv_body(const GemvParams& p) {
         const int kc = k < p.K ? k : p.K - 1;
         const bf16_t raw = p.x[(int64_t)r * p.ldx + kc];
         float xf = bf16_lo((uint32_t)__builtin_bit_cast(uint16_t, raw));
-        if (p.gamma) {
-            // rstd of row r from the partials (every wave sums the same <= 64 numbers along the same tree)
-            float t = lane < p.ss_n ? p.ss_in[(int64_t)r * p.ss_n + lane] : 0.0f;
-            for (int m = 1; m < 64; m <<= 1) t += shfl_xor_f(t, m);
-            const float rstd = 1.0f / sqrtf(t / (float)p.K + p.eps);
-            const float g = bf16_lo((uint32_t)__builtin_bit_cast(uint16_t, p.gamma[kc]));
-            xf = (float)(bf16_t)((float)(bf16_t)(xf * rstd) * g);
-        }
+        if (p.gamma) xf = gemv_norm(xf, gemv_row_rstd(p, r, lane), bf16_lo((uint32_t)__builtin_bit_cast(uint16_t, p.gamma[kc])));
         xv[r] = k < p.K ? xf : 0.0f;
     }
-    float acc[R][8];
-    for (int r = 0; r < R; ++r)
-        for (int j = 0; j < 8; ++j) acc[r][j] = 0.0f;
-    const bf16_t* wp = p.w[mi] + n;
+    typename W::Acc acc[R];
+    for (int r = 0; r < R; ++r) W::zero(acc[r]);
+    const typename W::Elem* wp = W::matrix(pp, mi) + n;
 #pragma unroll
     for (int i0 = 0; i0 < kGemvRPW; i0 += 8) {
-        u32x4 wv[8];
+        typename W::Load wv[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const int k = k0 + i0 + u;
-            wv[u] = global_load_b128(wp + (int64_t)(k < p.K ? k : p.K - 1) * N);        // rows past K meet x = 0
+            wv[u] = W::load(wp + (int64_t)(k < p.K ? k : p.K - 1) * N);        // rows past K meet x = 0
         }
 #pragma unroll
-        for (int u = 0; u < 8; ++u)
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const float xs = lane_value(xv[r], i0 + u);
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    acc[r][2 * c] = fmaf(xs, bf16_lo(wv[u][c]), acc[r][2 * c]);
-                    acc[r][2 * c + 1] = fmaf(xs, bf16_hi(wv[u][c]), acc[r][2 * c + 1]);
-                }
-            }
+        for (int u = 0; u < 8; ++u) W::fma(acc, wv[u], xv, i0 + u);
     }
     // waves 1..3 hand their sums to wave 0 through LDS; wave 0 adds them in wave order
     if (wave > 0) {
         for (int r = 0; r < R; ++r) {
             const lds_t slot = lds + (uint32_t)(((wave - 1) * R + r) * kGemvNT + lane * 8) * 4;
-            lds_write_f32x4(slot, f32x4{acc[r][0], acc[r][1], acc[r][2], acc[r][3]});
-            lds_write_f32x4(slot + 16, f32x4{acc[r][4], acc[r][5], acc[r][6], acc[r][7]});
+            for (int j = 0; j < 2; ++j) lds_write_f32x4(slot + 16 * j, W::quad(acc[r], j));
         }
     }
     block_sync();
     if (wave == 0 && n_ok) {
+        f32x4 sc[2] = {};                          // the group's scale of each of the lane's columns
+        if constexpr (W::kScaled)
+            for (int j = 0; j < 2; ++j) sc[j] = W::scale(pp, mi, (int64_t)ks * N + n + 4 * j);
         for (int r = 0; r < R; ++r) {
-            f32x4 lo = {acc[r][0], acc[r][1], acc[r][2], acc[r][3]}, hi = {acc[r][4], acc[r][5], acc[r][6], acc[r][7]};
-            for (int w = 0; w < 3; ++w) {
-                const lds_t slot = lds + (uint32_t)((w * R + r) * kGemvNT + lane * 8) * 4;
-                lo = lo + lds_read_f32x4(slot);
-                hi = hi + lds_read_f32x4(slot + 16);
-            }
             float* dst = p.part + p.part_off[mi] + ((int64_t)ks * R + r) * N + n;
-            global_store_f32x4(dst, lo);
-            global_store_f32x4(dst + 4, hi);
+            for (int j = 0; j < 2; ++j) {
+                f32x4 s = W::quad(acc[r], j);
+                for (int w = 0; w < 3; ++w) s = s + lds_read_f32x4(lds + (uint32_t)((w * R + r) * kGemvNT + lane * 8) * 4 + 16 * j);
+                if constexpr (W::kScaled) s = s * sc[j];          // once per partial: the scale is a power of two
+                global_store_f32x4(dst + 4 * j, s);
+            }
         }
     }
 }
 
-LWM_KERNEL(kGemvThreads) void gemv_bf16_kernel(GemvParams p) {
-    switch (p.R) {            // (uniform; the row count is a compile-time constant inside each body)
-        case 1: gemv_body<1>(p); break;
-        case 2: gemv_body<2>(p); break;
-        case 3: gemv_body<3>(p); break;
-        default: gemv_body<4>(p); break;
+template <class W>
+LWM_DEVICE void gemv_by_rows(const typename W::Params& p) {
+    switch (W::g(p).R) {      // (uniform; the row count is a compile-time constant inside each body)
+        case 1: gemv_body<W, 1>(p); break;
+        case 2: gemv_body<W, 2>(p); break;
+        case 3: gemv_body<W, 3>(p); break;
+        default: gemv_body<W, 4>(p); break;
     }
 }
+
+LWM_KERNEL(kGemvThreads) void gemv_bf16_kernel(GemvParams p) { gemv_by_rows<GemvBf16Format>(p); }
 
 // y[r, n..n+3] = sum over the KS partials.  Eight lanes per output quad: lane j adds partials j, j+8, ... (all
 // its loads in flight at once), then the eight sums meet by xor-shuffles -- a FIXED tree, so the result is

@@ -1,6 +1,6 @@
-// gemv_w8.h -- 8-bit (OCP e4m3fn) decode weights: the quantiser and the GEMV that streams them.  Requires wave_ops.h +
-// gemv.h (GemvParams, the K partition, gemv_reduce_kernel) + attn_decode.h (unpack_bf16x8, f32x2, fma2) + attn_decode_kv8.h
-// (cvt_e4m3x2_lo/hi, pack_e4m3x4) + attn_prefill_kv8.h (global_load_b64).
+// gemv_w8.h -- 8-bit (OCP e4m3fn) decode weights: the quantiser and the weight format of the GEMV that streams them.
+// Requires wave_ops.h + gemv.h (GemvParams, gemv_body, gemv_by_rows, gemv_reduce_kernel) + attn_decode.h (unpack_bf16x8,
+// f32x2, fma2) + attn_decode_kv8.h (cvt_e4m3x2_lo/hi, pack_e4m3x4) + attn_prefill_kv8.h (global_load_b64).
 //
 // Why: the projections of a cached-decode step stream every weight once per token (gemv.h); the bf16 kernel is
 // HBM-bound, so the lever left is the number of bytes.  Per (K, N) kernel the pack holds K * N e4m3 bytes and one f32
@@ -12,8 +12,8 @@
 //   amax over the rows of the group that exist; s = the smallest power of two with amax / s <= 448, clamped to
 //   [2^-126, 2^127] (amax == 0: s = 1); q = e4m3(w / s), round to nearest even.
 //
-// Why the bits agree with the bf16 kernel on the rounded weights e4m3(q) * s: the K partition, the order of every fmaf
-// chain and of the wave sum are gemv_body's, and with a power-of-two s (no overflow, no underflow)
+// Why the bits agree with the bf16 kernel on the rounded weights e4m3(q) * s: both kernels are gemv_body (one K partition,
+// one order of every fmaf chain and of the wave sum), and with a power-of-two s (no overflow, no underflow)
 // fmaf(x, q * s, a * s) == s * fmaf(x, q, a) -- so multiplying the summed tile by s once gives the bf16 kernel's partial.
 #pragma once
 
@@ -26,103 +26,48 @@ namespace lwm {
 constexpr int kGemvW8CPL = 8;                   // columns per lane = bytes per load
 constexpr int kGemvW8NT = 64 * kGemvW8CPL;      // columns of W per workgroup (= kGemvNT)
 
+static_assert(kGemvW8NT == kGemvNT && kGemvW8CPL == 8, "gemv_body's column tile");
+
 struct GemvW8Params {
     GemvParams g;                          // w[] unused; everything else as the bf16 kernel has it (the reduce kernel takes g)
     const uint8_t* q[kGemvMaxMats];        // [K, N_i] e4m3 bytes
     const float* scale[kGemvMaxMats];      // [KS, N_i]
 };
 
-template <int R>
-LWM_DEVICE void gemv_w8_body(const GemvW8Params& pp) {
-    const GemvParams& p = pp.g;
-    const lds_t lds = dyn_lds();
-    const int tid = thread_idx();
-    const int wave = wave_uniform(tid >> 6), lane = tid & 63;
-    int mi = 0;                                    // which matrix this workgroup belongs to (uniform)
-    for (int i = 1; i < p.nmat; ++i) mi = block_idx_x() >= p.blk0[i] ? i : mi;
-    const int N = p.N[mi];
-    const int nbn = (N + kGemvW8NT - 1) / kGemvW8NT;
-    const int bl = block_idx_x() - p.blk0[mi];
-    const int ks = bl / nbn, nb = bl % nbn;
-    const int k0 = ks * kGemvKT + wave * kGemvRPW;
-    int n = nb * kGemvW8NT + lane * kGemvW8CPL;
-    const bool n_ok = n < N;
-    n = n_ok ? n : N - kGemvW8CPL;                 // (clamped: the loads stay inside the matrix and the scale table)
-    // this wave's 32 x values per row r, one per lane (lanes 32..63 repeat): gemv_body's expression and tree
-    float xv[R];
-    for (int r = 0; r < R; ++r) {
-        const int k = k0 + (lane & (kGemvRPW - 1));
-        const int kc = k < p.K ? k : p.K - 1;
-        const bf16_t raw = p.x[(int64_t)r * p.ldx + kc];
-        float xf = bf16_lo((uint32_t)__builtin_bit_cast(uint16_t, raw));
-        if (p.gamma) {
-            float t = lane < p.ss_n ? p.ss_in[(int64_t)r * p.ss_n + lane] : 0.0f;
-            for (int m = 1; m < 64; m <<= 1) t += shfl_xor_f(t, m);
-            const float rstd = 1.0f / sqrtf(t / (float)p.K + p.eps);
-            const float g = bf16_lo((uint32_t)__builtin_bit_cast(uint16_t, p.gamma[kc]));
-            xf = (float)(bf16_t)((float)(bf16_t)(xf * rstd) * g);
-        }
-        xv[r] = k < p.K ? xf : 0.0f;
+// The e4m3 weight format of gemv_body (gemv.h): one 8-byte load per row, the accumulators as pairs (columns 2j, 2j+1 of the
+// lane's 8) for the packed FMAs, one multiply by the group's scale when the partial is finished.
+struct GemvW8Format {
+    using Params = GemvW8Params;
+    using Elem = uint8_t;
+    using Load = u32x2;
+    using Acc = f32x2[4];
+    static constexpr bool kScaled = true;
+    LWM_DEVICE static const GemvParams& g(const Params& p) { return p.g; }
+    LWM_DEVICE static const Elem* matrix(const Params& p, int mi) { return p.q[mi]; }
+    LWM_DEVICE static Load load(const Elem* at) { return global_load_b64(at); }
+    LWM_DEVICE static void zero(Acc& a) {
+        for (int j = 0; j < 4; ++j) a[j] = f32x2{0.0f, 0.0f};
     }
-    f32x2 acc[R][4];                               // columns 2j, 2j+1 of the lane's 8
-    for (int r = 0; r < R; ++r)
-        for (int j = 0; j < 4; ++j) acc[r][j] = f32x2{0.0f, 0.0f};
-    const uint8_t* wp = pp.q[mi] + n;
+    template <int R>
+    LWM_DEVICE static void fma(Acc (&a)[R], const Load& w, const float (&xv)[R], int i) {
 #pragma unroll
-    for (int i0 = 0; i0 < kGemvRPW; i0 += 8) {
-        u32x2 wv[8];
+        for (int c = 0; c < 2; ++c) {
+            const f32x2 lo = cvt_e4m3x2_lo(w[c]), hi = cvt_e4m3x2_hi(w[c]);
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int k = k0 + i0 + u;
-            wv[u] = global_load_b64(wp + (int64_t)(k < p.K ? k : p.K - 1) * N);        // rows past K meet x = 0
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const f32x2 lo = cvt_e4m3x2_lo(wv[u][c]), hi = cvt_e4m3x2_hi(wv[u][c]);
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const float xs = lane_value(xv[r], i0 + u);
-                    const f32x2 x2 = {xs, xs};
-                    acc[r][2 * c] = fma2(x2, lo, acc[r][2 * c]);
-                    acc[r][2 * c + 1] = fma2(x2, hi, acc[r][2 * c + 1]);
-                }
-            }
-    }
-    // waves 1..3 hand their sums to wave 0 through LDS; wave 0 adds them in wave order
-    if (wave > 0) {
-        for (int r = 0; r < R; ++r) {
-            const lds_t slot = lds + (uint32_t)(((wave - 1) * R + r) * kGemvW8NT + lane * kGemvW8CPL) * 4;
-            for (int j = 0; j < 2; ++j)
-                lds_write_f32x4(slot + 16 * j, f32x4{acc[r][2 * j][0], acc[r][2 * j][1], acc[r][2 * j + 1][0], acc[r][2 * j + 1][1]});
-        }
-    }
-    block_sync();
-    if (wave == 0 && n_ok) {
-        f32x4 sc[2];                               // the group's scale of each of the lane's columns
-        for (int j = 0; j < 2; ++j) sc[j] = global_load_f32x4(pp.scale[mi] + (int64_t)ks * N + n + 4 * j);
-        for (int r = 0; r < R; ++r) {
-            float* dst = p.part + p.part_off[mi] + ((int64_t)ks * R + r) * N + n;
-            for (int j = 0; j < 2; ++j) {
-                f32x4 s = {acc[r][2 * j][0], acc[r][2 * j][1], acc[r][2 * j + 1][0], acc[r][2 * j + 1][1]};
-                for (int w = 0; w < 3; ++w)
-                    s = s + lds_read_f32x4(lds + (uint32_t)((w * R + r) * kGemvW8NT + lane * kGemvW8CPL) * 4 + 16 * j);
-                global_store_f32x4(dst + 4 * j, s * sc[j]);       // once per partial: s is a power of two
+            for (int r = 0; r < R; ++r) {
+                const float xs = lane_value(xv[r], i);
+                const f32x2 x2 = {xs, xs};
+                a[r][2 * c] = fma2(x2, lo, a[r][2 * c]);
+                a[r][2 * c + 1] = fma2(x2, hi, a[r][2 * c + 1]);
             }
         }
     }
-}
+    LWM_DEVICE static f32x4 quad(const Acc& a, int j) { return f32x4{a[2 * j][0], a[2 * j][1], a[2 * j + 1][0], a[2 * j + 1][1]}; }
+    LWM_DEVICE static f32x4 scale(const Params& p, int mi, int64_t at) { return global_load_f32x4(p.scale[mi] + at); }
+};
 
 // dynamic LDS: 3 * R * kGemvW8NT * 4 bytes (the host sizes it by the row count)
-LWM_KERNEL(kGemvThreads) void gemv_w8_kernel(GemvW8Params p) {
-    switch (p.g.R) {          // (uniform; the row count is a compile-time constant inside each body)
-        case 1: gemv_w8_body<1>(p); break;
-        case 2: gemv_w8_body<2>(p); break;
-        case 3: gemv_w8_body<3>(p); break;
-        default: gemv_w8_body<4>(p); break;
-    }
-}
+LWM_KERNEL(kGemvThreads) void gemv_w8_kernel(GemvW8Params p) { gemv_by_rows<GemvW8Format>(p); }
 
 // ------------------------------------------------------------------ quantiser
 struct W8QuantParams {

@@ -54,4 +54,4 @@ def gemm_rows_fused(x, kernels, *, norm=None, residual=None, want_ss=False, out_
     the same arguments, fusions and reduction; the kernels are still streamed once.  x must be 16-byte aligned with a row
     stride that is a multiple of 8 elements.  A row's result does not depend on how many rows ride with it."""
     from . import llama_ops
-    return llama_ops._fused_call(True, x, kernels, norm, residual, want_ss, out_dtype)
+    return llama_ops._fused_call(llama_ops.BF16, True, x, kernels, norm, residual, want_ss, out_dtype)

@@ -13,6 +13,7 @@ arithmetic minus the roundings to bf16) and of the attention op (csrc/attn_f32.h
 from __future__ import annotations
 
 import ctypes as C
+import typing
 
 import numpy as np
 import torch
@@ -347,36 +348,68 @@ def swiglu(a, b):
 _GEMV_WS = {}
 
 
-def _gemv_check(x, kernels, out_dtype):
-    """x (rows, K) bf16 with contiguous rows, 1..3 contiguous bf16 (K, N_i) kernels, all on x's ROCm device -> (rows, K)"""
-    if x.dim() != 2 or not x.is_cuda or x.dtype != torch.bfloat16 or x.stride(1) != 1:
-        raise ValueError("gemv: x must be a bf16 (rows, K) ROCm tensor with contiguous rows")
+def _is_dev(t):
+    return torch.is_tensor(t) and t.is_cuda
+
+
+class ProjFormat(typing.NamedTuple):
+    """What tells the weight formats apart in the front end of the weight-streaming projections: BF16 here, w8.W8"""
+    args: type                  # the ctypes struct of the fused entries
+    entries: tuple              # their names: (lwm_gemv_fused_*, lwm_gemm_rows_fused_*)
+    who: str                    # opens the refusals of the operand checks ...
+    fused: tuple                # ... and those of the two wrappers: (gemv_fused*, gemm_rows_fused*)
+    noun: str                   # "kernel" / "pack"
+    matrix: typing.Callable     # (i, m, x, K) -> N_i, or a ValueError: the check of matrix i
+    fill: typing.Callable       # (a, i, m): w[i] (and w_scale[i]) of the args struct
+    checks_ss: bool             # a want_ss the entry cannot serve is refused here (else by the library)
+
+
+def _bf16_matrix(i, k, x, K):
+    if not _is_dev(k) or k.dim() != 2 or k.device != x.device or k.dtype != torch.bfloat16 or not k.is_contiguous() or k.shape[0] != K:
+        raise ValueError(f"gemv: kernels[{i}] must be a contiguous bf16 ({K}, N) tensor on {x.device}, got "
+                         f"{tuple(k.shape)} {k.dtype} on {k.device}")
+    return int(k.shape[1])
+
+
+def _bf16_fill(a, i, k):
+    a.w[i] = k.data_ptr()
+
+
+BF16 = ProjFormat(_capi.LwmGemvArgs, ("lwm_gemv_fused_bf16", "lwm_gemm_rows_fused_bf16"), "gemv", ("gemv_fused", "gemm_rows_fused"),
+                  "kernel", _bf16_matrix, _bf16_fill, False)
+
+
+def _gemv_check(fmt, x, mats, out_dtype):
+    """x (rows, K) bf16 with contiguous rows, 1..3 matrices of `fmt` with K rows, all on x's ROCm device -> (rows, K, [N_i])"""
+    if not _is_dev(x) or x.dim() != 2 or x.dtype != torch.bfloat16 or x.stride(1) != 1:
+        raise ValueError(f"{fmt.who}: x must be a bf16 (rows, K) ROCm tensor with contiguous rows")
     rows, K = x.shape
-    if not 1 <= len(kernels) <= 3:
-        raise ValueError("gemv: one to three kernels per call")
-    for i, k in enumerate(kernels):
-        if k.dim() != 2 or not _on(k, x) or k.dtype != torch.bfloat16 or not k.is_contiguous() or k.shape[0] != K:
-            raise ValueError(f"gemv: kernels[{i}] must be a contiguous bf16 ({K}, N) tensor on {x.device}, got "
-                             f"{tuple(k.shape)} {k.dtype} on {k.device}")
+    if not 1 <= len(mats) <= 3:
+        raise ValueError(f"{fmt.who}: one to three {fmt.noun}s per call")
+    Ns = [fmt.matrix(i, m, x, K) for i, m in enumerate(mats)]
     if out_dtype not in _DTYPES:
-        raise ValueError("gemv: out_dtype must be torch.bfloat16 or torch.float32")
-    return rows, K
+        raise ValueError(f"{fmt.who}: out_dtype must be torch.bfloat16 or torch.float32")
+    return rows, K, Ns
+
+
+def _gemv_buffers(L, x, rows, K, Ns, out_dtype, rows_entry=False):
+    """-> (the workspace of this shape, fresh outputs [(rows, N_i)])"""
+    key = (x.device, rows, K, tuple(Ns)) + (("rows",) if rows_entry else ())
+    ws = _GEMV_WS.get(key)
+    if ws is None:                     # (one workspace per shape: a hipGraph replays with the pointers it captured)
+        need = sum((L.lwm_gemm_rows_workspace_bytes if rows_entry else L.lwm_gemv_workspace_bytes)(rows, K, N) for N in Ns)
+        ws = _GEMV_WS[key] = torch.empty(max(need, 16), dtype=torch.uint8, device=x.device)
+    return ws, [torch.empty(rows, N, dtype=out_dtype, device=x.device) for N in Ns]
 
 
 def gemv_multi(x, kernels, out_dtype=torch.bfloat16):
     """x (rows <= 4, K) bf16 against 1..3 kernels (K, N_i) bf16 that share it -> [(rows, N_i)] in `out_dtype`
     (bf16 or f32) through ONE lwm_gemv_multi_bf16 call: every kernel streamed once from HBM, f32 accumulation
     along a fixed tree."""
-    rows, K = _gemv_check(x, kernels, out_dtype)
+    rows, K, Ns = _gemv_check(BF16, x, kernels, out_dtype)
     L = lib()
     n = len(kernels)
-    Ns = [int(k.shape[1]) for k in kernels]
-    key = (x.device, rows, K, tuple(Ns))
-    ws = _GEMV_WS.get(key)
-    if ws is None:                     # (one workspace per shape: a hipGraph replays with the pointers it captured)
-        need = sum(L.lwm_gemv_workspace_bytes(rows, K, N) for N in Ns)
-        ws = _GEMV_WS[key] = torch.empty(need, dtype=torch.uint8, device=x.device)
-    ys = [torch.empty(rows, N, dtype=out_dtype, device=x.device) for N in Ns]
+    ws, ys = _gemv_buffers(L, x, rows, K, Ns, out_dtype)
     f32 = out_dtype == torch.float32
     vp = C.c_void_p * n
     w_arr = vp(*[k.data_ptr() for k in kernels])
@@ -396,52 +429,54 @@ def gemv_fused(x, kernels, *, norm=None, residual=None, want_ss=False, out_dtype
     norm = (ss (rows, n <= 64) f32 partial sums of squares of x's rows, weight (K,) bf16, eps): RMSNorm on load;
     residual (rows, N) bf16 (one kernel): y = bf16(bf16(x @ W) + residual); want_ss: also return the (rows, N / 128)
     partial sums of squares of y for the next norm.  -> [y_i] or ([y_i], ss)."""
-    return _fused_call(False, x, kernels, norm, residual, want_ss, out_dtype)
+    return _fused_call(BF16, False, x, kernels, norm, residual, want_ss, out_dtype)
 
 
-def _fused_call(rows_entry, x, kernels, norm, residual, want_ss, out_dtype):
-    rows, K = _gemv_check(x, kernels, out_dtype)
-    L = lib()
-    n = len(kernels)
-    Ns = [int(k.shape[1]) for k in kernels]
+def _fused_call(fmt, rows_entry, x, mats, norm, residual, want_ss, out_dtype):
+    """lwm_gemv_fused_* / lwm_gemm_rows_fused_* (rows_entry) over the matrices of `fmt`; every check before any allocation"""
+    rows, K, Ns = _gemv_check(fmt, x, mats, out_dtype)
+    n = len(mats)
+    who = fmt.fused[0]
     if rows_entry:
         if not 1 <= rows <= 32:
-            raise ValueError(f"gemm_rows_fused: {rows} rows (1..32)")
+            raise ValueError(f"{fmt.fused[1]}: {rows} rows (1..32)")
         if not rows_x_ok(x):
-            raise ValueError("gemm_rows_fused: x must be 16-byte aligned with a row stride that is a multiple of 8 elements")
-    key = (x.device, rows, K, tuple(Ns)) + (("rows",) if rows_entry else ())
-    ws = _GEMV_WS.get(key)
-    if ws is None:                     # (one workspace per shape: a hipGraph replays with the pointers it captured)
-        need = sum((L.lwm_gemm_rows_workspace_bytes if rows_entry else L.lwm_gemv_workspace_bytes)(rows, K, N) for N in Ns)
-        ws = _GEMV_WS[key] = torch.empty(need, dtype=torch.uint8, device=x.device)
-    ys = [torch.empty(rows, N, dtype=out_dtype, device=x.device) for N in Ns]
-    a = _capi.LwmGemvArgs()
+            raise ValueError(f"{fmt.fused[1]}: x must be 16-byte aligned with a row stride that is a multiple of 8 elements")
+    on = lambda t: _is_dev(t) and t.device == x.device
+    if norm is not None:
+        ss, w, eps = norm
+        if not on(ss) or ss.dtype != torch.float32 or not ss.is_contiguous() or ss.dim() != 2 or ss.shape[0] != rows or \
+                not 1 <= ss.shape[1] <= 64:
+            raise ValueError(f"{who}: norm ss must be a contiguous f32 ({rows}, n <= 64) tensor on {x.device}")
+        if not on(w) or w.dtype != torch.bfloat16 or not w.is_contiguous() or w.numel() != K:
+            raise ValueError(f"{who}: norm weight must be a contiguous bf16 tensor of {K} elements on {x.device}")
+    if residual is not None:
+        if n != 1 or not on(residual) or residual.dtype != torch.bfloat16 or tuple(residual.shape) != (rows, Ns[0]) or \
+                residual.stride(1) != 1:
+            raise ValueError(f"{who}: residual goes with ONE {fmt.noun} and is a bf16 tensor of its output's shape on {x.device}")
+    if fmt.checks_ss and want_ss and (n != 1 or Ns[0] % 128 or out_dtype != torch.bfloat16):
+        raise ValueError(f"{who}: want_ss goes with ONE {fmt.noun}, a bf16 output and N % 128 == 0")
+    L = lib()
+    ws, ys = _gemv_buffers(L, x, rows, K, Ns, out_dtype, rows_entry)
+    a = fmt.args()
     a.x, a.ldx, a.nmat, a.rows, a.K = x.data_ptr(), x.stride(0), n, rows, K
     a.workspace = ws.data_ptr()
-    for i in range(n):
-        a.w[i], a.N[i] = kernels[i].data_ptr(), Ns[i]
+    for i, m in enumerate(mats):
+        fmt.fill(a, i, m)
+        a.N[i] = Ns[i]
         if out_dtype == torch.float32:
             a.y_f32[i] = ys[i].data_ptr()
         else:
             a.y[i], a.ldy[i] = ys[i].data_ptr(), Ns[i]
     if norm is not None:
-        ss, w, eps = norm
-        if not _on(ss, x) or ss.dtype != torch.float32 or not ss.is_contiguous() or ss.dim() != 2 or ss.shape[0] != rows or \
-                not 1 <= ss.shape[1] <= 64:
-            raise ValueError(f"gemv_fused: norm ss must be a contiguous f32 ({rows}, n <= 64) tensor on {x.device}")
-        if not _on(w, x) or w.dtype != torch.bfloat16 or not w.is_contiguous() or w.numel() != K:
-            raise ValueError(f"gemv_fused: norm weight must be a contiguous bf16 tensor of {K} elements on {x.device}")
         a.norm_weight, a.ss_in, a.ss_n, a.eps = w.data_ptr(), ss.data_ptr(), ss.shape[1], float(eps)
     if residual is not None:
-        if n != 1 or not _on(residual, x) or residual.dtype != torch.bfloat16 or tuple(residual.shape) != (rows, Ns[0]) or \
-                residual.stride(1) != 1:
-            raise ValueError(f"gemv_fused: residual goes with ONE kernel and is a bf16 tensor of its output's shape on {x.device}")
         a.residual[0], a.ldres[0] = residual.data_ptr(), residual.stride(0)
     ss_out = None
     if want_ss:
         ss_out = torch.empty(rows, Ns[0] // 128, dtype=torch.float32, device=x.device)
         a.ss_out = ss_out.data_ptr()
-    name = "lwm_gemm_rows_fused_bf16" if rows_entry else "lwm_gemv_fused_bf16"
+    name = fmt.entries[1 if rows_entry else 0]
     _capi.check(L, getattr(L, name)(C.byref(a), _stream_ptr()), name)
     return (ys, ss_out) if want_ss else ys
 

@@ -1,6 +1,7 @@
 """The checks of lwm_gemm_rows_fused_bf16 / lwm_gemm_rows_fused_w8 (csrc/gemm_rows.h), written once over a small buffer
 backend so that tests/test_emu_rows.py (host emulation, numpy buffers) and tests/test_gpu_rows.py (device buffers) run the
-same code.  TEST INFRASTRUCTURE ONLY.
+same code.  The refusal table runs against lwm_gemv_fused_bf16 / lwm_gemv_fused_w8 too (entry="gemv"), with what those
+entries answer differently written down beside it.  TEST INFRASTRUCTURE ONLY.
 
 A backend has lib() -> the bound C ABI, buf(array) -> a guarded, initialised buffer with .ptr, .read() (a numpy copy) and
 .intact() (both guard bands untouched), and sync().  Every buffer a call can write is poison-filled first; run() asserts
@@ -335,7 +336,7 @@ def check_row_independence(B, K, Ns, with_fused):
 def valid_args(B, w8, rows=5, K=64, N=128):
     bufs = dict(x=B.buf(np.zeros((rows, K), np.uint16)), w=B.buf(np.zeros((K, N), np.uint8 if w8 else np.uint16)),
                 s=B.buf(np.ones((1, N), np.float32)), y=B.buf(poison((rows, N), np.uint16)), yf=B.buf(poison((rows, N), np.float32)),
-                work=B.buf(poison((rows * N + TAIL,), np.float32)), res=B.buf(np.zeros((rows, N), np.uint16)),
+                work=B.buf(poison((2 * rows * N + TAIL,), np.float32)), res=B.buf(np.zeros((rows, N), np.uint16)),
                 gam=B.buf(np.zeros((K,), np.uint16)), ss=B.buf(np.ones((rows, 4), np.float32)), sso=B.buf(poison((rows, 1), np.float32)))
     a = (_capi.LwmGemvW8Args if w8 else _capi.LwmGemvArgs)()
     a.x, a.ldx, a.nmat, a.rows, a.K = bufs["x"].ptr, K, 1, rows, K
@@ -402,26 +403,65 @@ W8_REFUSALS = {
 }
 
 
-def check_refusal(B, w8, name):
+# What the GEMV entries (lwm_gemv_fused_bf16 / _w8) answer differently: x and norm_weight are read by the element and a
+# residual belongs to its matrix, so these edits are ACCEPTED there; no rows is a call that does nothing; the limit is 4 rows.
+GEMV_ACCEPTS = ("misaligned x", "ldx % 8", "misaligned norm_weight", "residual with two matrices")
+GEMV_REFUSALS = {k: v for k, v in REFUSALS.items() if k not in GEMV_ACCEPTS + ("rows 0",)} | {
+    "rows 5": (EUNSUP, lambda a, b: setattr(a, "rows", 5)),
+}
+ENTRY_ROWS = {"rows": 5, "gemv": 2}
+
+
+def entry_fn(L, entry, w8):
+    """-> (the C entry, the tag that opens its lwm_last_error() texts)"""
+    if entry == "rows":
+        return (L.lwm_gemm_rows_fused_w8, b"gemm_rows_w8: ") if w8 else (L.lwm_gemm_rows_fused_bf16, b"gemm_rows: ")
+    return (L.lwm_gemv_fused_w8, b"gemv_w8: ") if w8 else (L.lwm_gemv_fused_bf16, b"gemv: ")
+
+
+def check_refusal(B, w8, name, entry="rows"):
     L = B.lib()
-    code, edit = (REFUSALS | W8_REFUSALS)[name]
-    a, bufs = valid_args(B, w8)
+    code, edit = (REFUSALS | GEMV_REFUSALS | W8_REFUSALS)[name]
+    assert name in W8_REFUSALS or name in (REFUSALS if entry == "rows" else GEMV_REFUSALS)
+    a, bufs = valid_args(B, w8, rows=ENTRY_ROWS[entry])
     edit(a, bufs)
-    fn, tag = (L.lwm_gemm_rows_fused_w8, b"gemm_rows_w8") if w8 else (L.lwm_gemm_rows_fused_bf16, b"gemm_rows")
+    fn, tag = entry_fn(L, entry, w8)
     assert fn(C.byref(a), None) == code
     B.sync()
-    assert L.lwm_last_error() and tag in L.lwm_last_error()
+    assert L.lwm_last_error() and L.lwm_last_error().startswith(tag)
     assert untouched(bufs)
 
 
-def check_accepted(B, w8):
+def check_gemv_accepts(B, w8, name):
+    """the edits of GEMV_ACCEPTS, which the rows entries refuse, run on the GEMV entries (x = 0 or a guard band's small
+    values against W = 0: every output is a zero); no rows: LWM_OK and nothing is written"""
+    L = B.lib()
+    a, bufs = valid_args(B, w8, rows=ENTRY_ROWS["gemv"])
+    fn, _ = entry_fn(L, "gemv", w8)
+    if name == "rows 0":
+        a.rows = 0
+        assert fn(C.byref(a), None) == _capi.LWM_OK
+        B.sync()
+        assert untouched(bufs)
+        return
+    REFUSALS[name][1](a, bufs)
+    assert fn(C.byref(a), None) == _capi.LWM_OK, L.lwm_last_error()
+    B.sync()
+    used = a.nmat * a.rows * a.N[0]                         # (K = 64: one partial per output)
+    assert (bufs["y"].read() == 0).all() and (bufs["yf"].read() == 0).all() and is_poison(bufs["work"].read()[used:])
+    assert all(b.intact() for b in bufs.values())
+
+
+def check_accepted(B, w8, entry="rows"):
     """... so the table above is not vacuous; a null struct is refused"""
     L = B.lib()
-    a, bufs = valid_args(B, w8)
-    fn = L.lwm_gemm_rows_fused_w8 if w8 else L.lwm_gemm_rows_fused_bf16
+    rows = ENTRY_ROWS[entry]
+    a, bufs = valid_args(B, w8, rows=rows)
+    fn, tag = entry_fn(L, entry, w8)
     assert fn(C.byref(a), None) == _capi.LWM_OK
     B.sync()
-    assert (bufs["y"].read() == 0).all() and (bufs["yf"].read() == 0).all() and is_poison(bufs["work"].read()[-TAIL:])
+    assert (bufs["y"].read() == 0).all() and (bufs["yf"].read() == 0).all() and is_poison(bufs["work"].read()[rows * 128:])
     assert all(b.intact() for b in bufs.values())
-    assert fn(None, None) == EINVAL
-    assert L.lwm_gemm_rows_workspace_bytes(5, 64, 128) == 5 * 128 * 4 and L.lwm_gemm_rows_workspace_bytes(0, 64, 128) == 0
+    assert fn(None, None) == EINVAL and L.lwm_last_error().startswith(tag)
+    ws = L.lwm_gemm_rows_workspace_bytes if entry == "rows" else L.lwm_gemv_workspace_bytes
+    assert ws(rows, 64, 128) == rows * 128 * 4 and ws(0, 64, 128) == 0

@@ -70,6 +70,29 @@ def test_the_unedited_arguments_are_accepted(w8):
     RC.check_accepted(B, w8)
 
 
+# ---------------------------------------------------------------- the same table against lwm_gemv_fused_bf16 / _w8
+@pytest.mark.parametrize("w8", [False, True], ids=["bf16", "w8"])
+@pytest.mark.parametrize("name", list(RC.GEMV_REFUSALS))
+def test_gemv_refusals_touch_nothing(name, w8):
+    RC.check_refusal(B, w8, name, entry="gemv")
+
+
+@pytest.mark.parametrize("name", list(RC.W8_REFUSALS))
+def test_gemv_w8_refusals_touch_nothing(name):
+    RC.check_refusal(B, True, name, entry="gemv")
+
+
+@pytest.mark.parametrize("w8", [False, True], ids=["bf16", "w8"])
+@pytest.mark.parametrize("name", ("rows 0",) + RC.GEMV_ACCEPTS)
+def test_gemv_accepts_what_the_rows_entries_refuse(name, w8):
+    RC.check_gemv_accepts(B, w8, name)
+
+
+@pytest.mark.parametrize("w8", [False, True], ids=["bf16", "w8"])
+def test_gemv_unedited_arguments_are_accepted(w8):
+    RC.check_accepted(B, w8, entry="gemv")
+
+
 def test_abi_mirror():
     L = B.lib()
     assert L.lwm_version() >= 560
