@@ -3,33 +3,49 @@
 // gfx950.  Requires wave_ops.h, attn_common.h, attn_fwd.h, attn_fwd64.h (f4_* instruction helpers) and attn_bwd.h (the
 // delta kernel, the layout of the row statistics).
 //
+// Matrix instruction of both kernels: v_mfma_f32_16x16x32_bf16 (the forward uses 32x32x16).  At its power limit the chip
+// holds a higher clock on this shape -- same FLOP, same cycles per FLOP, 7 - 18 % more FLOP/s on random operands
+// (profiles/r09_dq16.md, profiles/r17_dkdv16.md) -- so a unit is the 32 x 32 one cut into 16 x 16 tiles at the same
+// bytes and registers.  Operand maps (lane l: c = l & 15, g = l >> 4): A holds row c, k = 8g .. 8g+7; B holds column c,
+// the same k; C / D hold column c, rows 4g .. 4g+3.
+//
 // dK/dV: replaces the dk / dv part of the custom-VJP backward of `ringattention` (call site lwm/llama.py:539-569;
 // SURVEY.md Appendix A.1): p from the saved LSE, dv += p^T do, dp = do v^T, ds = p * (dp - rowsum(do * o)),
-// dk += ds^T q * scale.
+// dk += ds^T q * scale.  It is the mirror of the dQ kernel below (keys <-> queries, K | V <-> Q | dO).
 //
-// Workgroup = 4 waves = 128 keys; a wave owns 32 keys and the SIMD's whole register file: its K and V fragments (B
-// operands, 32 + 32 registers) and the f32 dK^T / dV^T accumulators (64 + 64) live in the accumulator file -- the
-// forward's budget of 192 AGPRs -- so the only LDS traffic of the tile loop is the streamed operand: Q / dO row
-// fragments for S and dP, Q^T / dO^T transposed fragments for dK and dV, one fragment per MFMA, every address
-// register-resident (no v_xor).  Q / dO arrive by LDS-DMA in steps of 64 queries through a ring of four 32-KiB
-// slots: the pieces of step i+2 are issued in the first phase of step i and have landed, for every wave, at the
-// barrier that ends step i -- a whole step before their first reader, which is what lets the last phase of step
-// i+1 request the first fragments of step i+2 across the barrier.  The row statistics (attn_bwd.h: -lse * log2 e,
-// -delta, padded) travel the same way, one dword per lane.
+// Workgroup = 4 waves = 128 keys; a wave owns 32 keys = two halves kh of 16 and the SIMD's whole register file: its K
+// and V fragments (B operands, 32 + 32 registers) and the f32 dK^T / dV^T accumulators (64 + 64) live in the
+// accumulator file -- 192 AGPRs -- so the only LDS traffic of the tile loop is the streamed operand, every address
+// register-resident (no v_xor).  Q / dO arrive by LDS-DMA in steps of 64 queries through a ring of four 32-KiB slots:
+// the pieces of step i+2 are issued in the first phase of step i and have landed, for every wave, at the barrier that
+// ends step i -- a whole step before their first reader, which is what lets the last phase of step i+1 request the
+// first fragments of step i+2 across the barrier.  The row statistics (attn_bwd.h: -lse * log2 e, -delta, padded)
+// travel the same way, one dword per lane.
 //
-// A unit = 32 queries x the wave's 32 keys = two phases of 16 MFMAs, written as `asm volatile` statements in program
-// order (attn_fwd64.h explains why), with the vector work placed in the gaps:
+// A unit = 32 queries (two halves qh of 16) x the wave's 32 keys = two phases of 32 MFMAs, written as `asm volatile`
+// statements in program order (attn_fwd64.h explains why), with the vector work placed in the gaps:
 //
-//   phase   matrix pipe (consecutive MFMAs never share an accumulator)      vector pipe (same wave)
-//   X(u)    S(u) = Q(u) K^T  and  dP'(u) = dO(u) V^T - delta, alternating   P(u-1) -> bf16, dS(u-1) = p dP'(u-1) -> bf16
-//   Y(u)    dV^T += dO(u-1)^T P(u-1), dK^T += Q(u-1)^T dS(u-1), 8 tuples    t = S(u) c - lse2, p(u) = exp2(t)
+//   phase   matrix pipe (neighbours share an operand, never an accumulator)        vector pipe (same wave)
+//   X(u)    S(u)[qh][kh] = Q(u) K^T and dP'(u) = dO(u) V^T - delta: 16 row          the vector work of unit u-1 continues:
+//           fragments (ds_read_b128, 8 Q + 8 dO), each feeds the two kh: 32         dS = p dP', P and dS -> bf16
+//   Y(u)    dV^T[db < 8][kh] += dO(u-1)^T(db) P(u-1)[kh], dK^T the same with Q^T    t = S(u) c - lse2, p(u) = exp2(t)
+//           and dS: 16 transposed fragments (2 x ds_read_b64_tr_b16), each
+//           feeds the two kh: 32
 //
-// The products lag one unit, so every phase has fillers -- 32 VALU per 16 MFMAs -- and S needs one register tile (dP'
-// two: the multiply of unit u-1 runs beside the chain of unit u).  -delta enters as the initial value of the dP
-// accumulator (the wave that carries the statistics negates it on its way to LDS; the unit before requests it into
-// the tuple), so the chain leaves dP' = dP - delta and dS is ONE multiply: 64 VALU per 32 MFMAs.
+// D leaves column = key and rows = queries 4g .. 4g+3 of the half, so lse2 and -delta are per-ROW values, loaded by row
+// group from the statistics slot: -delta enters as the C operand of the first MFMA of each dP chain, so the chain leaves
+// dP' = dP - delta and dS is ONE multiply: 64 VALU per 64 MFMAs.  The B operand of Y is the packed P (dS) of the subtiles
+// (qh = 0, kh) | (qh = 1, kh) as the MFMAs left them, which puts k-group g at queries {4g .. 4g+3, 16+4g .. 16+4g+3}: the
+// transposed read takes its first four queries from rows 4g .., its second four from rows 16+4g ...  The products lag one
+// unit; S needs one set of register tiles, dP' two (the multiply of unit u-1 runs beside the chains of unit u).
 //
 // LDS map: slot 0..3 = [Q tile 64 rows | dO tile 64 rows] (16 KiB each) | stats 0..3 = [nl2 64 | -delta 64 | seg_q 64]
+// Tile image of both kernels: 256-byte rows, slot s of row r at physical slot s ^ q4_swz(r).  The swizzle of attn_common.h
+// would leave both reads of this operand shape 2-way (the b128 lane groups take rows 0-3, 12-15 at one slot and rows 4-11
+// at its neighbour; a half-wave of the transposed read takes 8 consecutive rows x 32 bytes); this one has
+//   * q4_swz(r) ^ [4 <= r&15 < 12] a bijection of r & 15      -> the row reads are conflict-free,
+//   * q4_swz(r) >> 1 a bijection of r & 7                     -> the transposed reads are conflict-free
+// (q4_image_ok enumerates every lane group of every read of a unit at compile time).
 #pragma once
 
 namespace lwm {
@@ -43,49 +59,132 @@ constexpr int kD4SlotBytes = 2 * kD4TileBytes;           // Q | dO
 constexpr int kD4OffStat = kD4Slots * kD4SlotBytes;      // 128 KiB
 constexpr int kD4StatBytes = 3 * kD4BQ * 4;              // nl2 | delta | seg_q
 constexpr int kD4LdsBytes = kD4OffStat + kD4Slots * kD4StatBytes;
-// LDS fragments are requested kD4Ahead MFMAs before the MFMA that consumes them, through ONE register ring of eight
-// that all four phases share (fragment m of a unit lives in ring[m % 8]).
+// LDS fragments are requested kD4Ahead fragments before the MFMAs that consume them, through ONE register ring of
+// eight that all phases share (fragment m of a unit lives in ring[m % 8]).
 #ifndef LWM_D4_AHEAD
 #define LWM_D4_AHEAD 6
 #endif
 constexpr int kD4Ahead = LWM_D4_AHEAD;
 static_assert(kD4Ahead >= 1 && kD4Ahead <= 7, "prefetch distance in fragments");
-// Fragments are requested and consumed in PAIRS (the two chains of X, the two products of Y): both requests go out in
-// the even gap, and the pair's YOUNGER fragment is consumed first -- the s_waitcnt hipcc puts in front of that MFMA
-// covers the older one too, so there is one wait per two MFMAs.
+// Fragments are requested and consumed in PAIRS: both requests go out in one gap, and the pair's YOUNGER fragment is
+// consumed first -- the s_waitcnt hipcc puts in front of that MFMA covers the older one too.
 static_assert((kD4Ahead % 2) == 0, "paired requests need an even distance");
 
+// ---- the tile image (see the file header)
+constexpr int q4_swz_of(int row) {
+    const int r = row & 15;
+    return (((r & 7) << 1) | (r >> 3)) ^ ((r >= 4 && r < 12) ? 1 : 0);
+}
+LWM_DEVICE int q4_swz(int row) { return q4_swz_of(row); }
+LWM_DEVICE uint32_t q4_tile_off(int row, int slot) { return (uint32_t)(row * kRowBytes + ((slot ^ q4_swz(row)) << 4)); }
+// Every lane group of every read of a unit hits one address per bank (MI355X: 64 banks of 4 bytes for both reads; a
+// ds_read_b128 is served in four groups of 16 lanes -- {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32 --, a
+// ds_read_b64_tr_b16 in the two halves of the wave).  Row fragment: lane (c, g) reads slot 4 s + g of row c; transposed
+// fragment: lane t of group g reads 8 bytes at d 16 db + 4 (t & 3) of row 4 g + (t >> 2) (and of that row + 16).
+constexpr bool q4_image_ok() {
+    for (int s = 0; s < 4; ++s)
+        for (int grp = 0; grp < 4; ++grp) {
+            unsigned long long banks = 0;
+            for (int l = 0; l < 64; ++l) {
+                const int m = l & 31;
+                const bool first = m < 4 || (m >= 12 && m < 16) || (m >= 20 && m < 28);
+                if (2 * (l >> 5) + (first ? 0 : 1) != grp) continue;
+                const int slot = (4 * s + (l >> 4)) ^ q4_swz_of(l & 15);
+                const unsigned long long b = 0xFull << (4 * slot);
+                if (banks & b) return false;
+                banks |= b;
+            }
+            if (banks != ~0ull) return false;
+        }
+    for (int db = 0; db < 8; ++db)
+        for (int up = 0; up < 2; ++up)
+            for (int half = 0; half < 2; ++half) {
+                unsigned long long banks = 0;
+                for (int l = 32 * half; l < 32 * half + 32; ++l) {
+                    const int g = l >> 4, t = l & 15, row = 16 * up + 4 * g + (t >> 2);
+                    const int slot = (2 * db + ((t & 3) >> 1)) ^ q4_swz_of(row);
+                    const unsigned long long b = 0x3ull << (4 * slot + 2 * (t & 1));
+                    if (banks & b) return false;
+                    banks |= b;
+                }
+                if (banks != ~0ull) return false;
+            }
+    return true;
+}
+static_assert(q4_image_ok(), "a read of the Q | dO (K | V) image is bank-conflicted");
+
+// ---- the 16x16x32 statements of both kernels
+#ifdef LWM_EMU
+// host form of v_mfma_f32_16x16x32_bf16 from its operand maps (scripts/micro/mfma_timing.hip prints the device's;
+// tests/test_gpu_dq16.py holds the device kernel to the oracle the emulated one meets)
+LWM_DEVICE f32x4 mfma_16x16x32(bf16x8 a, bf16x8 b, f32x4 c) {
+    emu::Wave& w = emu::g_blk->waves[emu::g_lane->tid >> 6];
+    const int l = emu::g_lane->tid & 63;
+    w.a[l] = a;
+    w.b[l] = b;
+    emu::wave_sync();
+    f32x4 d;
+    const int col = l & 15, g = l >> 4;
+    for (int j = 0; j < 4; ++j) {
+        const int row = 4 * g + j;
+        float s = c[j];
+        for (int k = 0; k < 32; ++k) s += (float)w.a[(k >> 3) * 16 + row][k & 7] * (float)w.b[(k >> 3) * 16 + col][k & 7];
+        d[j] = s;
+    }
+    emu::wave_sync();
+    return d;
+}
+LWM_DEVICE void q4_mfma_first(f32x4& d, bf16x8 a, bf16x8 b) { d = mfma_16x16x32(a, b, f32x4{0.0f, 0.0f, 0.0f, 0.0f}); }
+LWM_DEVICE void q4_mfma(f32x4& d, bf16x8 a, bf16x8 b) { d = mfma_16x16x32(a, b, d); }
+LWM_DEVICE void q4_mfma_c_first(f32x4& d, bf16x8 a, bf16x8 b, const f32x4& c) { d = mfma_16x16x32(a, b, c); }
+LWM_DEVICE void q4_mfma_o(f32x4& d, bf16x8 a, bf16x8 b) { d = mfma_16x16x32(a, b, d); }
+LWM_DEVICE void q4_mfma_o_first(f32x4& d, bf16x8 a, bf16x8 b) { d = mfma_16x16x32(a, b, f32x4{0.0f, 0.0f, 0.0f, 0.0f}); }
+LWM_DEVICE void q4_opaque(f32x4 (&)[2]) {}
+LWM_DEVICE void q4_settle_t(f32x4 (&)[4]) {}
+LWM_DEVICE void q4_settle_acc(f32x4 (&)[16]) {}
+#else
+// the statements of attn_fwd64.h on the 16x16 shape: S chains (B from the accumulator file), the first MFMA of a dP
+// chain (C = the -delta tuple, two wait states in front, see d4_mfma_p_first), the products into the accumulator file
+LWM_DEVICE void q4_mfma_first(f32x4& d, bf16x8 a, bf16x8 b) {
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&v"(d) : "v"(a), "a"(b));
+}
+LWM_DEVICE void q4_mfma(f32x4& d, bf16x8 a, bf16x8 b) {
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "a"(b));
+}
+LWM_DEVICE void q4_mfma_c_first(f32x4& d, bf16x8 a, bf16x8 b, const f32x4& c) {
+    asm volatile("s_nop 1\n\tv_mfma_f32_16x16x32_bf16 %0, %1, %2, %3" : "=&v"(d) : "v"(a), "a"(b), "v"(c));
+}
+LWM_DEVICE void q4_mfma_o(f32x4& d, bf16x8 a, bf16x8 b) {
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(d) : "v"(a), "v"(b));
+}
+LWM_DEVICE void q4_mfma_o_first(f32x4& d, bf16x8 a, bf16x8 b) {
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&a"(d) : "v"(a), "v"(b));
+}
+// registers that hold the same value: hipcc must not know (it would keep one and copy it into a tuple in front of
+// every chain)
+LWM_DEVICE void q4_opaque(f32x4 (&x)[2]) { asm volatile("" : "+v"(x[0]), "+v"(x[1])); }
+LWM_DEVICE void q4_settle_t(f32x4 (&s)[4]) { asm volatile("s_nop 7\n\ts_nop 7" : "+v"(s[0]), "+v"(s[1]), "+v"(s[2]), "+v"(s[3])); }
+LWM_DEVICE void q4_settle_acc(f32x4 (&a)[16]) {
+    asm volatile("s_nop 7\n\ts_nop 7"
+                 : "+a"(a[0]), "+a"(a[1]), "+a"(a[2]), "+a"(a[3]), "+a"(a[4]), "+a"(a[5]), "+a"(a[6]), "+a"(a[7]), "+a"(a[8]),
+                   "+a"(a[9]), "+a"(a[10]), "+a"(a[11]), "+a"(a[12]), "+a"(a[13]), "+a"(a[14]), "+a"(a[15]));
+}
+#endif
+
+// ====================================================================================================== dK/dV
 struct D4Ctx {
-    uint32_t qa[8];             // Q row-fragment addresses (d step s), rows 0..31 of the CURRENT step's Q tile
-    uint32_t tlo[4], tup[4];    // transposed-fragment addresses (d block), rows 0..15 of the current step's Q tile
-    uint32_t plo[4], pup[4];    // the same in the PREVIOUS step's slot (the lagging dK of a step's first unit)
-    uint32_t stat;              // this step's statistics + 16 * hi
+    uint32_t qa[4];             // Q row-fragment addresses (d step s of 32), rows 0..15 of the CURRENT step's Q tile
+    uint32_t tlo[8];            // Q transposed-fragment addresses (d block of 16), rows 4g.. of the current step's Q tile
+    uint32_t plo[8];            // the same in the PREVIOUS step's slot (the lagging products of a step's first unit)
+    uint32_t stat;              // this step's statistics + 16 * g
     float c;                    // scale * log2(e)
-    int hi;
 };
 
 #ifdef LWM_EMU
-LWM_DEVICE void d4_mfma_p_first(f32x16& d, bf16x8 a, bf16x8 b) { d = mfma_32x32x16(a, b, d); }
-LWM_DEVICE void d4_mfma_o_first(f32x16& d, bf16x8 a, bf16x8 b) { d = mfma_32x32x16(a, b, zero_f32x16()); }
 LWM_DEVICE float d4_mul(float a, float b) { return a * b; }
 LWM_DEVICE void d4_dma_b32(uint32_t voff, const char* src, lds_t dst) { glds_load_b32(src + voff, dst); }
-LWM_DEVICE void d4_settle_t(f32x16&) {}
-LWM_DEVICE void d4_settle_acc(f32x16 (&)[4], f32x16 (&)[4]) {}
 LWM_DEVICE void d4_settle_acc4(f32x16 (&)[4]) {}
 #else
-// What hipcc does not know about an asm MFMA (cdna_hip_programming.md section 5.7 item 2): a register it has just
-// written itself -- a copy that moves a tuple into place, a zero it materialises late -- needs two wait states before
-// an MFMA reads it.  The two statements below are used where that can happen:
-//   * the first MFMA of a dP chain: its accumulator was filled with -delta by compiler-visible LDS loads, which hipcc
-//     may route through copies (it does in the prologue): the wait states stand in front of the MFMA;
-//   * the first product of the walk into each dK^T / dV^T tuple: C = 0 and an OUTPUT-only operand, so that no
-//     compiler-made zero is read at all.
-LWM_DEVICE void d4_mfma_p_first(f32x16& d, bf16x8 a, bf16x8 b) {
-    asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "a"(b));
-}
-LWM_DEVICE void d4_mfma_o_first(f32x16& d, bf16x8 a, bf16x8 b) {
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&a"(d) : "v"(a), "v"(b));
-}
 LWM_DEVICE float d4_mul(float a, float b) {
     float y;
     asm volatile("v_mul_f32 %0, %1, %2" : "=v"(y) : "v"(a), "v"(b));
@@ -98,18 +197,33 @@ LWM_DEVICE void d4_dma_b32(uint32_t voff, const char* src, lds_t dst) {
                        (uint32_t)__builtin_amdgcn_readfirstlane((int)a);
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1" ::"v"(voff), "s"(u), "s"(dst) : "memory");
 }
-LWM_DEVICE void d4_settle_t(f32x16& s) { asm volatile("s_nop 7\n\ts_nop 7" : "+v"(s)); }
-LWM_DEVICE void d4_settle_acc(f32x16 (&a)[4], f32x16 (&b)[4]) {
-    asm volatile("s_nop 7\n\ts_nop 7"
-                 : "+a"(a[0]), "+a"(a[1]), "+a"(a[2]), "+a"(a[3]), "+a"(b[0]), "+a"(b[1]), "+a"(b[2]), "+a"(b[3]));
-}
+// (gemm_wgrad.h: 32x32 tuples)
 LWM_DEVICE void d4_settle_acc4(f32x16 (&a)[4]) { asm volatile("s_nop 7\n\ts_nop 7" : "+a"(a[0]), "+a"(a[1]), "+a"(a[2]), "+a"(a[3])); }
 #endif
+// What hipcc does not know about an asm MFMA (cdna_hip_programming.md section 5.7 item 2): a register it has just
+// written itself -- a copy that moves a tuple into place, a zero it materialises late -- needs two wait states before
+// an MFMA reads it, and a register an MFMA writes is not ready when the MFMA has issued.  The statements below are used
+// where that can happen:
+//   * the first MFMA of a dP chain: its C operand, the -delta tuple, was filled by compiler-visible LDS loads, which
+//     hipcc may route through copies: two wait states stand in front of the MFMA;
+//   * the first product of the walk into each dK^T / dV^T tuple: C = 0 and an OUTPUT-only operand, so that no
+//     compiler-made zero is read at all;
+//   * where compiler-generated code reads the S tiles or the accumulators (the mask code, a control-flow merge, the
+//     epilogue): wait states in a statement that names the tuples, so that every later use follows them.  The
+//     accumulators take two statements (an asm statement has 30 operands at most): dK^T first -- the LAST four MFMAs
+//     of a Y phase and of the drain write dK^T tuples, the last write of a dV^T tuple lies four MFMAs further back.
+LWM_DEVICE void d4_mfma_p_first(f32x4& d, bf16x8 a, bf16x8 b, const f32x4& c) { q4_mfma_c_first(d, a, b, c); }
+LWM_DEVICE void d4_mfma_o_first(f32x4& d, bf16x8 a, bf16x8 b) { q4_mfma_o_first(d, a, b); }
+LWM_DEVICE void d4_settle_t(f32x4 (&s)[4]) { q4_settle_t(s); }
+LWM_DEVICE void d4_settle_acc(f32x4 (&dk)[16], f32x4 (&dv)[16]) {
+    q4_settle_acc(dk);
+    q4_settle_acc(dv);
+}
 
 // per-lane byte offsets of the wave's four pieces of a 64-row tile (piece = 4 rows = 1 KiB; wave w moves pieces
 // w, w+4, w+8, w+12: rows 4w + 16j + (l>>4)) relative to the step's first row, rows clamped to Sq-1 (rows past Sq
 // get nl2 = -inf through the statistics).  Lane l writes physical slot l&15 of its row, so it fetches logical slot
-// (l&15) ^ swz(row) -- the XOR swizzle applied on the SOURCE column.
+// (l&15) ^ q4_swz(row) -- the XOR swizzle applied on the SOURCE column.
 LWM_DEVICE void d4_stage_offsets(const AttnParams& p, int wave, int lane, int st, uint32_t (&vq)[4], uint32_t (&vdo)[4]) {
     const int slot = lane & 15;
     for (int j = 0; j < 4; ++j) {
@@ -117,71 +231,78 @@ LWM_DEVICE void d4_stage_offsets(const AttnParams& p, int wave, int lane, int st
         int qrow = st * kD4BQ + row;
         qrow = qrow < p.Sq ? qrow : p.Sq - 1;
         const int rel = qrow - st * kD4BQ;
-        const int col = (slot ^ swz(row)) << 3;
+        const int col = (slot ^ q4_swz(row)) << 3;
         vq[j] = (uint32_t)(((int64_t)rel * p.q_ss + col) * 2);
         vdo[j] = (uint32_t)(((int64_t)rel * p.do_ss + col) * 2);
     }
 }
 
-// fragment f of a unit (f = MFMA index 0..31; 32.. = the first fragments of the unit that follows):
-//   0..15   phase X: d step f>>1; even = Q row fragment (S), odd = dO row fragment (dP)
-//   16..31  phase Y: j = f-16, (q step (j>>3)&1, d block (j>>1)&3) of the PREVIOUS unit; even = dO^T (dV), odd = Q^T (dK)
+// fragment f of a unit (32 per unit, each feeds the MFMAs of the two key halves; 32.. = the first fragments of the unit
+// that follows).  A PAIR of fragments is one tensor: the MFMAs of a pair run (f+1, kh 0), (f+1, kh 1), (f, kh 1),
+// (f, kh 0) -- neighbours share A, then B, then A -- and the next pair is the other tensor.
+//   0..15   phase X: pair f>>1 = (d step s = f>>2, tensor (f>>1)&1: 0 = Q row fragment (S), 1 = dO (dP')); query half f&1
+//   16..31  phase Y: j = f-16, pair j>>1 = (tensor (j>>1)&1: 0 = dO^T (dV), 1 = Q^T (dK)); d block 2 (j>>2) + (j&1) of the
+//           PREVIOUS unit: queries 4g.. (first read) and 16+4g.. (second read)
 // cx.qa points at the step's slot for HALF = 0 and for the X phase of HALF = 1; it has moved on to the next step's slot
 // when the Y phase of HALF = 1 requests f >= 32.
 template <int HALF>
 LWM_DEVICE bf16x8 d4_frag(const D4Ctx& cx, int f) {
     if (f >= 32) {
         const int g = f - 32;
-        return lds_read_b128(cx.qa[g >> 1] + (g & 1) * kD4TileBytes + (HALF == 0 ? 32 * kRowBytes : 0));
+        return lds_read_b128(cx.qa[g >> 2] + ((g >> 1) & 1) * kD4TileBytes + (g & 1) * 16 * kRowBytes + (HALF == 0 ? 32 * kRowBytes : 0));
     }
-    if (f < 16) return lds_read_b128(cx.qa[f >> 1] + (f & 1) * kD4TileBytes + HALF * 32 * kRowBytes);
-    const int j = f - 16, t = (j >> 3) & 1, db = (j >> 1) & 3;
+    if (f < 16) return lds_read_b128(cx.qa[f >> 2] + ((f >> 1) & 1) * kD4TileBytes + (f & 1) * 16 * kRowBytes + HALF * 32 * kRowBytes);
+    const int j = f - 16, db = 2 * (j >> 2) + (j & 1);
     // the previous unit: the second half of the previous step's tiles for HALF = 0, the first half of this step's
-    const uint32_t alo = HALF == 0 ? cx.plo[db] : cx.tlo[db];
-    const uint32_t aup = HALF == 0 ? cx.pup[db] : cx.tup[db];
-    const uint32_t off = ((j & 1) ? 0 : kD4TileBytes) + (HALF == 0 ? 32 * kRowBytes : 0) + 16 * t * kRowBytes;
-    bf16x4 lo = lds_read_tr16(alo + off);
-    bf16x4 up = lds_read_tr16(aup + off);
+    const uint32_t a = (HALF == 0 ? cx.plo[db] : cx.tlo[db]) + (HALF == 0 ? 32 * kRowBytes : 0) + (((j >> 1) & 1) ? 0 : kD4TileBytes);
+    bf16x4 lo = lds_read_tr16(a);
+    bf16x4 up = lds_read_tr16(a + 16 * kRowBytes);
     bf16x8 o;
     o[0] = lo[0]; o[1] = lo[1]; o[2] = lo[2]; o[3] = lo[3];
     o[4] = up[0]; o[5] = up[1]; o[6] = up[2]; o[7] = up[3];
     return o;
 }
 
-// ---- where the vector work of a unit u goes.  Gaps are numbered over the two phases that host it: G = 0..15 = the
-// gaps of Y(u) (its S and dP' tiles are complete), G = 16..31 = the gaps of X(u+1).  Per element e (16 per lane) /
-// per pair i (8 per lane):
-//   F(e)  t = S c - lse2          needs S(u): G >= 1 (the chains have left the pipe), G <= 15 (X(u+1) overwrites S)
-//   E(e)  p = exp2(t)             >= 1 gap behind F(e) (and a transcendental's result is not read in the next slot)
-//   M(e)  dS = p dP'              >= 1 gap behind E(e)
-//   P(i)  P words -> bf16         >= 1 gap behind E(2i), E(2i+1); the products of Y(u) still read the OLD P: word i of
-//   D(i)  dS words -> bf16           the first half (i < 4) from G = 8, of the second from G = 16; D(i) likewise, >= 1 gap
-//                                    behind M(2i), M(2i+1); everything done by G = 29 (Y(u+1) reads them at G = 32)
-// d4_sched_ok() checks the table at compile time.
+// ---- where the vector work of a unit u goes.  Gaps are numbered over the two phases that host it: G = 0..31 = the
+// gaps of Y(u) (gap = behind that MFMA), G = 32..63 = the gaps of X(u+1).  An MFMA holds the vector issue for 8 of its 16
+// cycles, so a gap takes two plain VALU or one v_exp_f32 beside its LDS read.  Per element e (16 per lane: key half
+// e >> 3, query half (e >> 2) & 1, row e & 3 of the group -- score tile e >> 2) / per pair i (8 per lane):
+//   F(e)  t = S c - lse2          3 <= G (three MFMAs between the end of the S chains and their first reader), G <= 31
+//                                 (X(u+1) overwrites S)
+//   E(e)  p = exp2(t)             behind F(e)
+//   M(e)  dS = p dP'              behind E(e)
+//   P(i)  P words -> bf16         behind E(2i), E(2i+1); the products of Y(u) read the OLD words to their last MFMA:
+//   D(i)  dS words -> bf16        G >= 32; D(i) behind M(2i), M(2i+1); everything done by G = 61
+// The words of a key half are four consecutive packed registers, ready as the B operand of Y.
 struct D4Sched {
     int F[16], E[16], M[16], P[8], D[8];
 };
 constexpr bool d4_sched_ok(const D4Sched& c) {
+    int load[64] = {};
     for (int e = 0; e < 16; ++e) {
-        if (c.F[e] < 1 || c.F[e] > 15) return false;
-        if (c.E[e] <= c.F[e] || c.M[e] <= c.E[e] || c.M[e] > 29) return false;
+        if (c.F[e] < 3 || c.F[e] > 31 || c.E[e] <= c.F[e] || c.M[e] <= c.E[e] || c.M[e] > 61) return false;
+        load[c.F[e]] += 1;
+        load[c.E[e]] += 2;
+        load[c.M[e]] += 1;
     }
     for (int i = 0; i < 8; ++i) {
-        const int lo = i < 4 ? 8 : 16;
-        if (c.P[i] < lo || c.P[i] > 29 || c.P[i] <= c.E[2 * i] || c.P[i] <= c.E[2 * i + 1]) return false;
-        if (c.D[i] < lo || c.D[i] > 29 || c.D[i] <= c.M[2 * i] || c.D[i] <= c.M[2 * i + 1]) return false;
+        if (c.P[i] < 32 || c.P[i] > 61 || c.P[i] <= c.E[2 * i] || c.P[i] <= c.E[2 * i + 1]) return false;
+        if (c.D[i] < 32 || c.D[i] > 61 || c.D[i] <= c.M[2 * i] || c.D[i] <= c.M[2 * i + 1]) return false;
+        load[c.P[i]] += 1;
+        load[c.D[i]] += 1;
     }
+    for (int g = 0; g < 64; ++g)
+        if (load[g] > 2) return false;      // (in units of a plain VALU's issue; an exp counts two)
     return true;
 }
-// exponentials in Y (beside the transposed reads), multiplies and packs in X (three other placements measured within
-// the run-to-run noise: profiles/r04_backward.md)
+// exponentials in Y (beside the transposed reads), multiplies and packs in X
 constexpr D4Sched kD4Sched = {
-    /* F */ {1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8},
-    /* E */ {2, 3, 4, 4, 5, 6, 7, 7, 8, 9, 9, 10, 10, 11, 11, 12},
-    /* M */ {16, 16, 17, 17, 18, 18, 19, 19, 20, 20, 21, 21, 22, 22, 23, 23},
-    /* P */ {16, 17, 18, 19, 20, 21, 22, 23},
-    /* D */ {24, 25, 26, 27, 28, 29, 29, 29}};
-static_assert(d4_sched_ok(kD4Sched), "filler schedule violates a dependency");
+    /* F */ {3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10},
+    /* E */ {11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26},
+    /* M */ {27, 27, 28, 28, 29, 29, 30, 30, 31, 31, 32, 32, 33, 33, 34, 34},
+    /* P */ {35, 35, 36, 36, 37, 37, 38, 38},
+    /* D */ {39, 39, 40, 40, 41, 41, 42, 42}};
+static_assert(d4_sched_ok(kD4Sched), "filler schedule violates a dependency or the issue budget of a gap");
 
 // the LDS-DMA pieces one step issues (all wave-uniform but the offsets): Q and dO of the step two ahead
 struct D4Dma {
@@ -192,24 +313,25 @@ struct D4Dma {
 
 // Live state of a wave across units.
 struct D4Regs {
-    f32x16 s;               // S tile (MFMA result, read-only for the vector pipe)
-    f32x16 dp[2];           // dP' tiles by unit parity: preloaded with -delta (in C/D register order), then the dP chain
-    float nl[16];           // -lse * log2(e) of the unit's rows, C/D register order
+    f32x4 s[4];             // S tiles [2 kh + qh] (MFMA results, read-only for the vector pipe but for the masks)
+    f32x4 dp[2][4];         // dP' tiles by unit parity
+    f32x4 ndl[2];           // -delta of rows 4g.. of the unit's query halves: the C operand that starts each dP chain
+    float nl[8];            // -lse * log2(e) of the same rows [4 qh + j]
     float t[16];            // exponents, then p
     float ds[16];           // dS = p * dP'
-    bf16x8 pb[2], dsb[2];   // P / dS as B operands (q steps of 16)
+    bf16x8 pb[2], dsb[2];   // P / dS as B operands, by key half
     uint32_t pw[8], dw[8];  // their words as they are packed (a half is handed over when its fourth word is in)
     bf16x8 fr[8];           // the fragment ring
 };
 
-// the vector work scheduled in gap G; dpu = the dP' tile of the unit being finished
-template <int G>
-LWM_DEVICE void d4_fillers(const D4Ctx& cx, D4Regs& rg, const f32x16& dpu) {
+// the vector work scheduled in gap G for the unit of parity PAR
+template <int G, int PAR>
+LWM_DEVICE void d4_fillers(const D4Ctx& cx, D4Regs& rg) {
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-        if (kD4Sched.F[e] == G) rg.t[e] = f4_fma(rg.s[e], cx.c, rg.nl[e]);
+        if (kD4Sched.F[e] == G) rg.t[e] = f4_fma(rg.s[e >> 2][e & 3], cx.c, rg.nl[4 * ((e >> 2) & 1) + (e & 3)]);
         if (kD4Sched.E[e] == G) rg.t[e] = f4_exp2(rg.t[e]);
-        if (kD4Sched.M[e] == G) rg.ds[e] = d4_mul(rg.t[e], dpu[e]);
+        if (kD4Sched.M[e] == G) rg.ds[e] = d4_mul(rg.t[e], rg.dp[PAR][e >> 2][e & 3]);
     }
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -228,132 +350,152 @@ LWM_DEVICE void d4_fillers(const D4Ctx& cx, D4Regs& rg, const f32x16& dpu) {
         if (ld == G) rg.dsb[h] = __builtin_bit_cast(bf16x8, u32x4{rg.dw[4 * h], rg.dw[4 * h + 1], rg.dw[4 * h + 2], rg.dw[4 * h + 3]});
     }
 }
-// dispatch a loop index to the compile-time gap (the loops are fully unrolled: the chain folds to one call)
-template <int G0, int N>
-LWM_DEVICE void d4_fill_at(int g, const D4Ctx& cx, D4Regs& rg, const f32x16& dpu) {
-    if constexpr (N > 0) {
-        if (g == G0) d4_fillers<G0>(cx, rg, dpu);
-        else d4_fill_at<G0 + 1, N - 1>(g, cx, rg, dpu);
-    }
-}
 
-// -delta of a unit's rows -> the dP tuple that unit's chain will accumulate into (stat = statistics slot + 16 hi)
-template <int HALF>
-LWM_DEVICE void d4_load_ndelta(uint32_t stat, f32x16& dp, int g) {
-    const f32x4 v = lds_read_f32x4(stat + kD4BQ * 4 + HALF * 32 * 4 + 8 * g * 4);
-    dp[4 * g + 0] = v[0]; dp[4 * g + 1] = v[1]; dp[4 * g + 2] = v[2]; dp[4 * g + 3] = v[3];
-}
-
-// Phase X of unit u (16 MFMAs): S(u) = Q K^T and dP'(u) = dO V^T - delta, the two chains ALTERNATING -- a dependent
-// MFMA that does not follow its predecessor back to back waits for the whole chain before it (MI355X_MICROARCH.md,
-// per-instruction constants: +43 cycles for the first instruction in between), an independent MFMA in between hides
-// that -- || the second half of unit u-1's vector work: P -> bf16, dS = p dP', dS -> bf16.
-// The first kD4Ahead fragments are ALREADY in the ring; the dP tuple holds -delta.
-template <int HALF, bool HAS_PREV, bool DMA>
+// Every MFMA index below is a template parameter (the phases are recursions, not loops): fragment, tile and filler
+// selection must be constants, or the register arrays they index go to scratch.
+//
+// Phase X of unit u (parity HALF): 32 MFMAs, fragment (M>>1)^1 (a pair is requested every fourth gap, its YOUNGER
+// fragment consumed first: one wait per four MFMAs), key half ((M>>1)^M)&1; fillers: gaps 32..63 of unit u-1.  A dependent
+// MFMA finds its predecessor eight MFMAs back.  The first kD4Ahead fragments are ALREADY in the ring, rg.ndl holds the
+// unit's -delta; the unit's -lse * log2 e is read here (needed from gap 3 of phase Y).
+template <int HALF, bool HAS_PREV, bool DMA, int M = 0>
 LWM_DEVICE void d4_x(const D4Ctx& cx, D4Regs& rg, const bf16x8 (&kf)[8], const bf16x8 (&vf)[8], const uint32_t (&vq)[4],
                      const uint32_t (&vdo)[4], const D4Dma& dm) {
-    f32x16& dpn = rg.dp[HALF];            // this unit's dP'
-    const f32x16& dpo = rg.dp[HALF ^ 1];  // the previous unit's
-#pragma unroll
-    for (int m = 0; m < 16; ++m) {
-        if ((m & 1) == 0) {
-            rg.fr[(m + kD4Ahead) & 7] = d4_frag<HALF>(cx, m + kD4Ahead);
-            rg.fr[(m + kD4Ahead + 1) & 7] = d4_frag<HALF>(cx, m + kD4Ahead + 1);
+    if constexpr (M < 32) {
+        if constexpr ((M & 3) == 0) {
+            constexpr int f0 = (M >> 1) + kD4Ahead;
+            rg.fr[f0 & 7] = d4_frag<HALF>(cx, f0);
+            sched_fence();      // (the pair in this order: the wait for the younger fragment then covers both)
+            rg.fr[(f0 + 1) & 7] = d4_frag<HALF>(cx, f0 + 1);
         }
-        if ((m & 3) == 2) {      // the unit's -lse * log2 e (needed from gap 1 of phase Y)
-            const int g = m >> 2;
-            const f32x4 v = lds_read_f32x4(cx.stat + HALF * 32 * 4 + 8 * g * 4);
-            rg.nl[4 * g + 0] = v[0]; rg.nl[4 * g + 1] = v[1]; rg.nl[4 * g + 2] = v[2]; rg.nl[4 * g + 3] = v[3];
+        if constexpr (M == 10 || M == 18) {
+            constexpr int qh = M == 18 ? 1 : 0;
+            const f32x4 v = lds_read_f32x4(cx.stat + (HALF * 32 + 16 * qh) * 4);
+            rg.nl[4 * qh + 0] = v[0]; rg.nl[4 * qh + 1] = v[1]; rg.nl[4 * qh + 2] = v[2]; rg.nl[4 * qh + 3] = v[3];
         }
         sched_fence();
         {
-            const int f = m ^ 1;      // the fragment this gap's MFMA consumes: even = Q (S), odd = dO (dP')
-            if (f == 0) f4_mfma_s_first(rg.s, rg.fr[0], kf[0]);
-            else if ((f & 1) == 0) f4_mfma_s(rg.s, rg.fr[f & 7], kf[f >> 1]);
-            else if (f == 1) d4_mfma_p_first(dpn, rg.fr[1], vf[0]);
-            else f4_mfma_s(dpn, rg.fr[f & 7], vf[f >> 1]);
+            constexpr int f = (M >> 1) ^ 1, qh = f & 1, kh = ((M >> 1) ^ M) & 1;
+            constexpr int s = f >> 2, t = 2 * kh + qh;
+            if constexpr (((f >> 1) & 1) == 0) {
+                if constexpr (s == 0) q4_mfma_first(rg.s[t], rg.fr[f & 7], kf[4 * kh]);
+                else q4_mfma(rg.s[t], rg.fr[f & 7], kf[4 * kh + s]);
+            } else {
+                if constexpr (s == 0) d4_mfma_p_first(rg.dp[HALF][t], rg.fr[f & 7], vf[4 * kh], rg.ndl[qh]);
+                else q4_mfma(rg.dp[HALF][t], rg.fr[f & 7], vf[4 * kh + s]);
+            }
         }
-        if (DMA && (m & 1)) {         // the wave's 4 Q and 4 dO pieces of the step two ahead, all in the step's first phase
-            const int j = m >> 2;
-            if ((m & 2) == 0) f4_dma1(vq[j], dm.q_src, dm.dst + 4096 * j);
+        if constexpr (DMA && (M & 3) == 3) {      // the wave's 4 Q and 4 dO pieces of the step two ahead, all in the step's first phase
+            constexpr int i = M >> 2, j = i >> 1;
+            if constexpr ((i & 1) == 0) f4_dma1(vq[j], dm.q_src, dm.dst + 4096 * j);
             else f4_dma1(vdo[j], dm.do_src, dm.dst + kD4TileBytes + 4096 * j);
         }
-        if (HAS_PREV) d4_fill_at<16, 16>(16 + m, cx, rg, dpo);
+        if constexpr (HAS_PREV) d4_fillers<32 + M, HALF ^ 1>(cx, rg);
         sched_fence();
+        d4_x<HALF, HAS_PREV, DMA, M + 1>(cx, rg, kf, vf, vq, vdo, dm);
     }
 }
 
-// masks of a unit on its scores (lwm/llama.py:572-592): query row (r&3) + 8 (r>>2) + 4 hi of the unit sees this lane's
-// key iff it is not before it (rel = key position - position of the unit's row 0 - 4 hi, clamped) and, with key meta,
+// masks of a unit on its scores (lwm/llama.py:572-592): query row 16 qh + 4g + j of the unit sees the lane's key of half
+// kh iff it is not before it (rel[kh] = key position - position of the unit's row 0 - 4g, clamped) and, with key meta,
 // shares its segment (kseg = kSegInvalid for a padded / out-of-range key)
 template <int HALF, bool HAS_META>
-LWM_DEVICE void d4_mask(const D4Ctx& cx, D4Regs& rg, int rel, int32_t kseg) {
+LWM_DEVICE void d4_mask(const D4Ctx& cx, f32x4 (&s)[4], const int (&rel)[2], const int32_t (&kseg)[2]) {
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        if (HAS_META) {
-            const u32x4 sg = lds_read_u32x4(cx.stat + 2 * kD4BQ * 4 + HALF * 32 * 4 + 8 * g * 4);
+    for (int qh = 0; qh < 2; ++qh) {
+        u32x4 sg = {0u, 0u, 0u, 0u};
+        if (HAS_META) sg = lds_read_u32x4(cx.stat + 2 * kD4BQ * 4 + HALF * 32 * 4 + 16 * qh * 4);
+#pragma unroll
+        for (int kh = 0; kh < 2; ++kh)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const bool vis = ((int32_t)sg[j] == kseg) && (8 * g + j >= rel);
-                rg.s[4 * g + j] = vis ? rg.s[4 * g + j] : -INFINITY;
+                const bool vis = (!HAS_META || (int32_t)sg[j] == kseg[kh]) && (16 * qh + j >= rel[kh]);
+                s[2 * kh + qh][j] = vis ? s[2 * kh + qh][j] : -INFINITY;
             }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) rg.s[4 * g + j] = (8 * g + j >= rel) ? rg.s[4 * g + j] : -INFINITY;
-        }
     }
 }
 
-// Phase Y of unit u (16 MFMAs): dV^T += dO(u-1)^T P(u-1) and dK^T += Q(u-1)^T dS(u-1), eight accumulators in turn  ||
-// the first half of unit u's vector work: t = S c - lse2 (from gap 1: the chains have left the pipe), p = exp2(t).
-// The last gaps request the first fragments of the unit that follows and its -delta (statn = the statistics slot
-// of that unit + 16 hi).
+// Phase Y of unit u: dV^T += dO(u-1)^T P(u-1) and dK^T += Q(u-1)^T dS(u-1), 32 MFMAs (fragment 16 + ((J>>1)^1), key half
+// ((J>>1)^J)&1; every accumulator once)  ||  gaps 0..31 of unit u.  The last gaps request the first fragments of the unit
+// that follows and its -delta (statn = the statistics slot of that unit + 16 g).
 // INIT: these are the first products of the walk (C = 0: the tuples are defined here).
-template <int HALF, bool HAS_PREV, bool NEXT, bool INIT>
-LWM_DEVICE void d4_y(const D4Ctx& cx, D4Regs& rg, f32x16 (&dk)[4], f32x16 (&dv)[4], uint32_t statn) {
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        const int m = 16 + j;
-        if ((j & 1) == 0 && (m + kD4Ahead < 32 || NEXT)) {
-            rg.fr[(m + kD4Ahead) & 7] = d4_frag<HALF>(cx, m + kD4Ahead);
-            rg.fr[(m + kD4Ahead + 1) & 7] = d4_frag<HALF>(cx, m + kD4Ahead + 1);
+template <int HALF, bool HAS_PREV, bool NEXT, bool INIT, int J = 0>
+LWM_DEVICE void d4_y(const D4Ctx& cx, D4Regs& rg, f32x4 (&dk)[16], f32x4 (&dv)[16], uint32_t statn) {
+    if constexpr (J < 32) {
+        if constexpr ((J & 3) == 0 && (16 + (J >> 1) + kD4Ahead < 32 || NEXT)) {
+            constexpr int f0 = 16 + (J >> 1) + kD4Ahead;
+            rg.fr[f0 & 7] = d4_frag<HALF>(cx, f0);
+            sched_fence();      // (the pair in this order: the wait for the younger fragment then covers both)
+            rg.fr[(f0 + 1) & 7] = d4_frag<HALF>(cx, f0 + 1);
         }
-        if (NEXT && j >= 12) d4_load_ndelta<HALF ^ 1>(statn, rg.dp[HALF ^ 1], j - 12);
+        if constexpr (NEXT && (J == 22 || J == 26)) {
+            constexpr int qh = J == 26 ? 1 : 0;
+            rg.ndl[qh] = lds_read_f32x4(statn + kD4BQ * 4 + ((HALF ^ 1) * 32 + 16 * qh) * 4);
+        }
         sched_fence();
-        if (HAS_PREV) {
-            const int jf = j ^ 1;      // the fragment consumed: even = dO^T (dV), odd = Q^T (dK)
-            if (INIT && jf < 8) {
-                if ((jf & 1) == 0) d4_mfma_o_first(dv[(jf >> 1) & 3], rg.fr[(16 + jf) & 7], rg.pb[0]);
-                else d4_mfma_o_first(dk[(jf >> 1) & 3], rg.fr[(16 + jf) & 7], rg.dsb[0]);
+        if constexpr (HAS_PREV) {
+            constexpr int jf = (J >> 1) ^ 1, kh = ((J >> 1) ^ J) & 1;
+            constexpr int db = 2 * (jf >> 2) + (jf & 1);
+            if constexpr (((jf >> 1) & 1) == 0) {
+                if constexpr (INIT) d4_mfma_o_first(dv[2 * db + kh], rg.fr[(16 + jf) & 7], rg.pb[kh]);
+                else q4_mfma_o(dv[2 * db + kh], rg.fr[(16 + jf) & 7], rg.pb[kh]);
             } else {
-                if ((jf & 1) == 0) f4_mfma_o(dv[(jf >> 1) & 3], rg.fr[(16 + jf) & 7], rg.pb[jf >> 3]);
-                else f4_mfma_o(dk[(jf >> 1) & 3], rg.fr[(16 + jf) & 7], rg.dsb[jf >> 3]);
+                if constexpr (INIT) d4_mfma_o_first(dk[2 * db + kh], rg.fr[(16 + jf) & 7], rg.dsb[kh]);
+                else q4_mfma_o(dk[2 * db + kh], rg.fr[(16 + jf) & 7], rg.dsb[kh]);
             }
         }
-        d4_fill_at<0, 16>(j, cx, rg, rg.dp[HALF]);
+        d4_fillers<J, HALF>(cx, rg);
         sched_fence();
+        d4_y<HALF, HAS_PREV, NEXT, INIT, J + 1>(cx, rg, dk, dv, statn);
     }
 }
 
 // the pipeline's tail: the second half of the last unit's vector work, then its dV / dK products (no fillers left).
-// PAR = the parity of the last unit (its dP' tuple); its tiles are addressed as the "previous unit" of a HALF = 0 unit.
-template <int PAR>
-LWM_DEVICE void d4_drain(const D4Ctx& cx, D4Regs& rg, f32x16 (&dk)[4], f32x16 (&dv)[4]) {
-#pragma unroll
-    for (int g = 16; g < 32; ++g) d4_fill_at<16, 16>(g, cx, rg, rg.dp[PAR]);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) rg.fr[j] = d4_frag<0>(cx, 16 + 8 * h + j);
-        sched_fence();
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int jj = 8 * h + j;
-            if ((jj & 1) == 0) f4_mfma_o(dv[(jj >> 1) & 3], rg.fr[j], rg.pb[jj >> 3]);
-            else f4_mfma_o(dk[(jj >> 1) & 3], rg.fr[j], rg.dsb[jj >> 3]);
-        }
-        sched_fence();
+// PAR = the parity of the last unit (its dP' tiles); its tiles are addressed as the "previous unit" of a HALF = 0 unit.
+template <int PAR, int G = 32>
+LWM_DEVICE void d4_drain_fill(const D4Ctx& cx, D4Regs& rg) {
+    if constexpr (G < 64) {
+        d4_fillers<G, PAR>(cx, rg);
+        d4_drain_fill<PAR, G + 1>(cx, rg);
     }
+}
+template <int H, int J = 0>
+LWM_DEVICE void d4_drain_mfma(D4Regs& rg, f32x4 (&dk)[16], f32x4 (&dv)[16]) {
+    if constexpr (J < 16) {
+        constexpr int jf = 8 * H + (J >> 1), kh = ((J >> 1) ^ J) & 1;
+        constexpr int db = 2 * (jf >> 2) + (jf & 1);
+        if constexpr (((jf >> 1) & 1) == 0) q4_mfma_o(dv[2 * db + kh], rg.fr[jf & 7], rg.pb[kh]);
+        else q4_mfma_o(dk[2 * db + kh], rg.fr[jf & 7], rg.dsb[kh]);
+        d4_drain_mfma<H, J + 1>(rg, dk, dv);
+    }
+}
+template <int PAR>
+LWM_DEVICE void d4_drain(const D4Ctx& cx, D4Regs& rg, f32x4 (&dk)[16], f32x4 (&dv)[16]) {
+    d4_drain_fill<PAR>(cx, rg);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) rg.fr[j] = d4_frag<0>(cx, 16 + j);
+    sched_fence();
+    d4_drain_mfma<0>(rg, dk, dv);
+    sched_fence();
+#pragma unroll
+    for (int j = 0; j < 8; ++j) rg.fr[j] = d4_frag<0>(cx, 24 + j);
+    sched_fence();
+    d4_drain_mfma<1>(rg, dk, dv);
+    sched_fence();
+}
+
+// a wave's dK^T or dV^T tiles -> its epilogue staging tile (attn_common.h, "epilogue staging": the same image as
+// epi_tile_write leaves, from the 16 x 16 accumulator layout): lane (c, g) holds, of tile [2 db + kh], the four columns
+// 16 db + 4g + 0..3 of row 16 kh + c (the 8 contiguous lanes of a ds_write_b128 group: 8 rows x 4 distinct banks of 32)
+LWM_DEVICE void d4_epi_tile_write(lds_t tb, const f32x4 (&acc)[16], float scale, int c, int g) {
+#pragma unroll
+    for (int db = 0; db < 8; ++db)
+#pragma unroll
+        for (int kh = 0; kh < 2; ++kh) {
+            const f32x4 a = acc[2 * db + kh];
+            lds_write_f32x4(tb + (uint32_t)((16 * kh + c) * kEpiRowBytes + (16 * db + 4 * g) * 4),
+                            f32x4{a[0] * scale, a[1] * scale, a[2] * scale, a[3] * scale});
+        }
 }
 
 // The epilogue of a key block: the wave's dK^T (scaled) and dV^T tiles, rows row0 .. row0 + 31 of (b, h), through the
@@ -362,7 +504,7 @@ LWM_DEVICE void d4_drain(const D4Ctx& cx, D4Regs& rg, f32x16 (&dk)[4], f32x16 (&
 // instructions share is read and computed ONCE (kernel arguments, the lane's first address of each buffer, the
 // strides): left inside the row loop, hipcc re-read carry_in / final_out / Sk behind a wait per row and rebuilt the
 // 64-bit address products -- 15 k cycles per key block (s_memtime), five times the data movement.
-LWM_DEVICE void d4_store_tiles(const AttnParams& p, lds_t tb, const f32x16 (&dk)[4], const f32x16 (&dv)[4], int b, int h,
+LWM_DEVICE void d4_store_tiles(const AttnParams& p, lds_t tb, const f32x4 (&dk)[16], const f32x4 (&dv)[16], int b, int h,
                                int row0, int lane) {
     const int l31 = lane & 31, hi = lane >> 5, col = l31 * 4;
     const int Sk = p.Sk;
@@ -373,7 +515,7 @@ LWM_DEVICE void d4_store_tiles(const AttnParams& p, lds_t tb, const f32x16 (&dk)
 #pragma unroll
     for (int which = 0; which < 2; ++which) {
         if (which) wave_lds_fence();        // (dK^T's rows have been read)
-        epi_tile_write(tb, which ? dv : dk, which ? 1.0f : p.scale, l31, hi);
+        d4_epi_tile_write(tb, which ? dv : dk, which ? 1.0f : p.scale, lane & 15, lane >> 4);
         wave_lds_fence();
         char* ap = (char*)(which ? p.dv_acc : p.dk_acc) + acc0;
         const int64_t o_ss = which ? p.dv_ss : p.dk_ss;
@@ -416,7 +558,7 @@ LWM_DEVICE void attn_bwd_dkdv4_body(const AttnParams& p) {
 #endif
     const lds_t lds = dyn_lds();
     const int tid = thread_idx();
-    const int wave = wave_uniform(tid >> 6), lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
+    const int wave = wave_uniform(tid >> 6), lane = tid & 63, l15 = lane & 15, g4 = lane >> 4;
 
     // ---- block -> (key block, head, batch): all key blocks of one (b,h) on one XCD, longest walks first
     const int nkb = (p.Sk + kD4BK - 1) / kD4BK;
@@ -436,24 +578,33 @@ LWM_DEVICE void attn_bwd_dkdv4_body(const AttnParams& p) {
     const bf16_t* vb = p.v + (int64_t)b * p.v_sb + (int64_t)h * p.v_sh;
     const bf16_t* dob = p.dout + (int64_t)b * p.do_sb + (int64_t)h * p.do_sh;
 
-    // ---- this lane's key: fragments straight into the accumulator file (a row past Sk re-reads the last row: its
-    // results are never stored)
-    const int k_row = kbi * kD4BK + wave * 32 + l31;
-    const bool k_ok = k_row < p.Sk;
-    const int kr = k_ok ? k_row : p.Sk - 1;
-    bf16x8 kf[8], vf[8];
-    for (int s = 0; s < 8; ++s) kf[s] = f4_load_agpr(kb + (int64_t)kr * p.k_ss + 16 * s + 8 * hi);
-    for (int s = 0; s < 8; ++s) vf[s] = f4_load_agpr(vb + (int64_t)kr * p.v_ss + 16 * s + 8 * hi);
+    // ---- this lane's two keys (row 16 kh + c of the wave's 32): fragments straight into the accumulator file (a row
+    // past Sk re-reads the last row: its results are never stored)
+    int k_row[2], kr[2];
+    bool k_ok[2];
+#pragma unroll
+    for (int kh = 0; kh < 2; ++kh) {
+        k_row[kh] = kbi * kD4BK + wave * 32 + 16 * kh + l15;
+        k_ok[kh] = k_row[kh] < p.Sk;
+        kr[kh] = k_ok[kh] ? k_row[kh] : p.Sk - 1;
+    }
+    bf16x8 kf[8], vf[8];        // [4 kh + s]: d step s of 32
+#pragma unroll
+    for (int i = 0; i < 8; ++i) kf[i] = f4_load_agpr(kb + (int64_t)kr[i >> 2] * p.k_ss + 32 * (i & 3) + 8 * g4);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) vf[i] = f4_load_agpr(vb + (int64_t)kr[i >> 2] * p.v_ss + 32 * (i & 3) + 8 * g4);
     const PosMap qm = q_map(p);
     const PosTab qt_ = load_postab(qm);                           // (register copies of the tables: prologue only)
     const int64_t k_base = pos_base(load_postab(k_map(p)), kbi * kD4BK);       // position of key row r of this workgroup = k_base + r
-    const int64_t k_pos = k_base + k_row;
-    int32_t kseg = 0;
+    int32_t kseg[2] = {0, 0};
     if (HAS_META) {
-        kseg = kSegInvalid;
-        if (k_ok) {
-            const bool valid = p.key_valid ? (p.key_valid[(int64_t)b * p.Sk + k_row] != 0) : true;
-            if (valid) kseg = p.seg_k ? p.seg_k[(int64_t)b * p.Sk + k_row] : 0;
+#pragma unroll
+        for (int kh = 0; kh < 2; ++kh) {
+            kseg[kh] = kSegInvalid;
+            if (k_ok[kh]) {
+                const bool valid = p.key_valid ? (p.key_valid[(int64_t)b * p.Sk + k_row[kh]] != 0) : true;
+                if (valid) kseg[kh] = p.seg_k ? p.seg_k[(int64_t)b * p.Sk + k_row[kh]] : 0;
+            }
         }
     }
 
@@ -472,11 +623,13 @@ LWM_DEVICE void attn_bwd_dkdv4_body(const AttnParams& p) {
     const int n = nst > st0 ? nst - st0 : 0;       // steps of the walk; walk index i -> step nst - 1 - i (descending:
                                                    // the key blocks resident on an XCD read the same tile at the same time)
 
-    f32x16 dk[4], dv[4];       // defined by the first products of the walk (d4_y<.., INIT>), or zero when there is no walk
+    f32x4 dk[16], dv[16];      // [2 db + kh]: rows 16 db + 4g + 0..3 of dK^T / dV^T for key 16 kh + c; defined by the first
+                               // products of the walk (d4_y<.., INIT>), or zero when there is no walk
     if (n == 0)
-        for (int i = 0; i < 4; ++i) {
-            dk[i] = zero_f32x16();
-            dv[i] = zero_f32x16();
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            dk[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            dv[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
         }
     if (n == 0) {       // (no walk: the fragments are unused, their loads are not left in flight)
         f4_load_agpr_wait8(kf);
@@ -485,19 +638,16 @@ LWM_DEVICE void attn_bwd_dkdv4_body(const AttnParams& p) {
 
     if (n > 0) {
         D4Ctx cx;
-        cx.hi = hi;
         cx.c = p.scale * kLog2e;
-        for (int s = 0; s < 8; ++s) cx.qa[s] = lds + tile_off(l31, 2 * s + hi);
-        {
-            const TrFragAddr t = frag_tr_addr(lds, lane);
-            for (int db = 0; db < 4; ++db) {
-                cx.tlo[db] = t.lo[db];
-                cx.tup[db] = t.up[db];
-                cx.plo[db] = t.lo[db];
-                cx.pup[db] = t.up[db];
-            }
+#pragma unroll
+        for (int s = 0; s < 4; ++s) cx.qa[s] = lds + q4_tile_off(l15, 4 * s + g4);
+#pragma unroll
+        for (int db = 0; db < 8; ++db) {
+            // lane t of a 16-lane group addresses query 4g + (t>>2), d 16 db + 4 (t&3): four queries x 16 d per group
+            cx.tlo[db] = lds + q4_tile_off(4 * g4 + (l15 >> 2), 2 * db + ((l15 & 3) >> 1)) + (l15 & 1) * 8;
+            cx.plo[db] = cx.tlo[db];
         }
-        cx.stat = lds + kD4OffStat + 16 * hi;
+        cx.stat = lds + kD4OffStat + 16 * g4;
 
         const int64_t q_step_bytes = (int64_t)kD4BQ * p.q_ss * 2, do_step_bytes = (int64_t)kD4BQ * p.do_ss * 2;
         uint32_t vq[4], vdo[4];
@@ -553,7 +703,9 @@ LWM_DEVICE void attn_bwd_dkdv4_body(const AttnParams& p) {
         // ub = 64 * step + 32 * half (steps descend, the halves of a step ascend); everything is clamped to 32 bits once.
         auto clamp32 = [](int64_t x) -> int { return x > (1 << 30) ? (1 << 30) : (x < -(1 << 30) ? -(1 << 30) : (int)x); };
         // positions relative to q_start; a unit's first query (row ub of the q block) sits at rel_pos(qm, ub)
-        const int k_rel = clamp32(k_pos - p.q_start) - 4 * hi;                                     // this lane's key
+        int k_rel[2];                                                                    // this lane's keys
+#pragma unroll
+        for (int kh = 0; kh < 2; ++kh) k_rel[kh] = clamp32(k_base + k_row[kh] - p.q_start) - 4 * g4;
         PosCursor qc = cursor_begin(qt_);
         auto q_rel_of = [&](int ub) -> int {             // (the walk descends: a compare while the unit is inside the piece)
             cursor_seek(qm, qc, ub);
@@ -564,32 +716,48 @@ LWM_DEVICE void attn_bwd_dkdv4_body(const AttnParams& p) {
         const int mask_end = p.causal ? 32 * tiles_reaching(qt_, 32, (p.Sq + 31) / 32, k_base + (int64_t)kbi * kD4BK + wave * 32 + 31 - 1) : 0;
         auto needs_causal = [&](int ub) -> bool { return ub < mask_end; };
         // the wave's 32 keys all valid and of one segment?  (then a step whose 64 queries carry it needs no segment test)
-        const int32_t own_seg = wave_uniform(kseg);
-        const bool own_uniform = HAS_META && !wave_any(kseg != own_seg || kseg == kSegInvalid);
-        auto rel_of = [&](int ub) -> int {
-            if (!p.causal) return -64;
-            const int64_t d = (int64_t)k_rel - q_rel_of(ub);
-            return d > 64 ? 64 : (d < -64 ? -64 : (int)d);
+        const int32_t own_seg = wave_uniform(kseg[0]);
+        const bool own_uniform = HAS_META && !wave_any(kseg[0] != own_seg || kseg[1] != own_seg || own_seg == kSegInvalid);
+        auto rel_of = [&](int ub, int (&rel)[2]) {
+            if (!p.causal) {
+                rel[0] = rel[1] = -64;
+                return;
+            }
+            const int qr = q_rel_of(ub);
+#pragma unroll
+            for (int kh = 0; kh < 2; ++kh) {
+                const int64_t d = (int64_t)k_rel[kh] - qr;
+                rel[kh] = d > 64 ? 64 : (d < -64 ? -64 : (int)d);
+            }
         };
 
         D4Regs rg;
-        rg.s = zero_f32x16();
-        rg.dp[0] = zero_f32x16();
-        rg.dp[1] = zero_f32x16();
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            rg.s[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            rg.dp[0][t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            rg.dp[1][t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        }
+#pragma unroll
         for (int r = 0; r < 16; ++r) {
-            rg.nl[r] = 0.0f;
             rg.t[r] = 0.0f;
             rg.ds[r] = 0.0f;
         }
+#pragma unroll
+        for (int r = 0; r < 8; ++r) rg.nl[r] = 0.0f;
+#pragma unroll
         for (int t = 0; t < 2; ++t) {
             rg.pb[t] = zero_bf16x8();
             rg.dsb[t] = zero_bf16x8();
         }
+#pragma unroll
         for (int j = 0; j < 8; ++j) rg.fr[j] = zero_bf16x8();
         D4Dma dm = {};
         // the first unit's fragments and -delta (every later unit finds them requested by the unit before it)
+#pragma unroll
         for (int j = 0; j < kD4Ahead; ++j) rg.fr[j] = d4_frag<0>(cx, j);
-        for (int g = 0; g < 4; ++g) d4_load_ndelta<0>(cx.stat, rg.dp[0], g);
+#pragma unroll
+        for (int qh = 0; qh < 2; ++qh) rg.ndl[qh] = lds_read_f32x4(cx.stat + kD4BQ * 4 + 16 * qh * 4);
 
         // Step i of the walk.  Its tiles are in slot i & 3; the address registers in cx point there and move on to the slot
         // of step i+1 (wrapping) as the step ends: the row-fragment addresses behind the last X phase (the Y phase after
@@ -601,11 +769,13 @@ LWM_DEVICE void attn_bwd_dkdv4_body(const AttnParams& p) {
     do {                                                                                                            \
         /* (the wait states sit in ONE statement on every path that needs them: with two, hipcc merges the tuples */ \
         /* of the two paths by copies placed right behind the last MFMA)                                         */ \
-        if (!(HAS_PREV_)) d4_settle_t(rg.s);     /* no MFMA stands between the S chain and its first reader */       \
+        if (!(HAS_PREV_)) d4_settle_t(rg.s);     /* no MFMA stands between the S chains and their first reader */    \
         if ((HAS_META && !uni_) || needs_causal(ub_)) {                                                             \
             if (HAS_PREV_) d4_settle_t(rg.s);                                                                       \
-            if (HAS_META && !uni_) d4_mask<HALF_, HAS_META>(cx, rg, rel_of(ub_), kseg);                             \
-            else d4_mask<HALF_, false>(cx, rg, rel_of(ub_), kseg);                                                  \
+            int rel_[2];                                                                                            \
+            rel_of(ub_, rel_);                                                                                      \
+            if (HAS_META && !uni_) d4_mask<HALF_, HAS_META>(cx, rg.s, rel_, kseg);                                  \
+            else d4_mask<HALF_, false>(cx, rg.s, rel_, kseg);                                                       \
         }                                                                                                           \
     } while (0)
         // (-DLWM_PROF builds, scripts/micro/attn_bench with LWM_PROF_DUMP=1: s_memtime laps of the pipelined steps of the
@@ -639,7 +809,7 @@ LWM_DEVICE void attn_bwd_dkdv4_body(const AttnParams& p) {
 #define LWM_D4_STEP(i, FIRST, PIPE)                                                                                 \
     do {                                                                                                            \
         if (PIPE) {                                                                                                 \
-            if (stat_on) d4_dma_b32(vstat, st_src2, stat_dst + (((i) + 2) & 3) * kD4StatBytes);        \
+            if (stat_on) d4_dma_b32(vstat, st_src2, stat_dst + (((i) + 2) & 3) * kD4StatBytes);                     \
             dm.q_src = q_src2;                                                                                      \
             dm.do_src = do_src2;                                                                                    \
             dm.dst = lds + (((i) + 2) & 3) * kD4SlotBytes + (uint32_t)wave * 1024;                                  \
@@ -649,20 +819,20 @@ LWM_DEVICE void attn_bwd_dkdv4_body(const AttnParams& p) {
         }                                                                                                           \
         const uint32_t d_ = (((i) & 3) == 3) ? (uint32_t)(-3 * kD4SlotBytes) : (uint32_t)kD4SlotBytes;             \
         const uint32_t e_ = (((i) & 3) == 3) ? (uint32_t)(-3 * kD4StatBytes) : (uint32_t)kD4StatBytes;             \
-        const int32_t segw_ = HAS_META ? seg_step_word(cx.stat - 16 * hi + 2 * kD4BQ * 4, lane) : 0;                \
+        const int32_t segw_ = HAS_META ? seg_step_word(cx.stat - 16 * g4 + 2 * kD4BQ * 4, lane) : 0;                \
         d4_x<0, !(FIRST), PIPE>(cx, rg, kf, vf, vq, vdo, dm);                                                       \
         const bool uni_ = HAS_META && seg_step_uniform(segw_, own_uniform, own_seg);                                \
         D4_LAP2(0);                                                                                                 \
         LWM_D4_MASK(0, !(FIRST), ub);                                                                               \
         D4_LAP2(1);                                                                                                 \
-        d4_y<0, !(FIRST), true, false>(cx, rg, dk, dv, cx.stat);                                                           \
+        d4_y<0, !(FIRST), true, false>(cx, rg, dk, dv, cx.stat);                                                    \
         D4_LAP2(2);                                                                                                 \
-        d4_x<1, true, false>(cx, rg, kf, vf, vq, vdo, dm);                                                           \
-        for (int s_ = 0; s_ < 8; ++s_) cx.qa[s_] += d_;                                                             \
+        d4_x<1, true, false>(cx, rg, kf, vf, vq, vdo, dm);                                                          \
+        for (int s_ = 0; s_ < 4; ++s_) cx.qa[s_] += d_;                                                             \
         D4_LAP2(3);                                                                                                 \
         LWM_D4_MASK(1, true, ub + 32);                                                                              \
         D4_LAP2(4);                                                                                                 \
-        d4_y<1, true, true, FIRST>(cx, rg, dk, dv, cx.stat + e_);                                                          \
+        d4_y<1, true, true, FIRST>(cx, rg, dk, dv, cx.stat + e_);                                                   \
         D4_LAP(5);                                                                                                  \
         ub -= kD4BQ;                                                                                                \
         /* wherever control flow merges behind a step (loop entry, loop exit, the short-walk branch) hipcc may */  \
@@ -672,11 +842,9 @@ LWM_DEVICE void attn_bwd_dkdv4_body(const AttnParams& p) {
         D4_LAP(6);                                                                                                  \
         block_sync_lds();                                                                                           \
         D4_LAP(7);                                                                                                  \
-        for (int db_ = 0; db_ < 4; ++db_) {                                                                         \
+        for (int db_ = 0; db_ < 8; ++db_) {                                                                         \
             cx.plo[db_] = cx.tlo[db_];                                                                              \
-            cx.pup[db_] = cx.tup[db_];                                                                              \
             cx.tlo[db_] += d_;                                                                                      \
-            cx.tup[db_] += d_;                                                                                      \
         }                                                                                                           \
         cx.stat += e_;                                                                                              \
         D4_LAP(8);                                                                                                  \
@@ -745,11 +913,7 @@ LWM_KERNEL(kD4Threads) void attn_bwd_dkdv4_meta_kernel(AttnParams p) { attn_bwd_
 // file header): p from the saved LSE, dp = do v^T, ds = p * (dp - delta), dq += ds k * scale.  Same contract,
 // operands, masks, carries and segment-block hints as the dK/dV kernel above.
 //
-// Matrix instruction: v_mfma_f32_16x16x32_bf16 (the dK/dV kernel and the forward use 32x32x16).  At its power limit
-// the chip holds a higher clock on this shape -- same FLOP, same cycles per FLOP, 7 - 18 % more FLOP/s on random
-// operands (profiles/r09_dq16.md) -- so the unit below is the old one cut into 16 x 16 tiles at the same bytes and
-// registers.  Operand maps (lane l: c = l & 15, g = l >> 4): A holds row c, k = 8g .. 8g+7; B holds column c, the same
-// k; C / D hold column c, rows 4g .. 4g+3.
+// Matrix instruction, operand maps and tile image: the file header.
 //
 // Workgroup = 4 waves = 128 queries; a wave owns 32 query rows = two halves qh of 16: their Q and dO fragments (B
 // operands, 32 + 32 registers) and the f32 dQ^T accumulator (64) live in the accumulator file.  Everything is computed
@@ -771,21 +935,11 @@ LWM_KERNEL(kD4Threads) void attn_bwd_dkdv4_meta_kernel(AttnParams p) { attn_bwd_
 // words of a step are staged through LDS by the threads themselves, as the forward does.
 //
 // LDS map: slot 0..3 = [K tile 64 rows | V tile 64 rows] (16 KiB each) | key meta 0..3 (64 words each)
-// Tile image: 256-byte rows, slot s of row r at physical slot s ^ q4_swz(r).  The swizzle of attn_common.h would leave
-// both reads of this operand shape 2-way (the b128 lane groups take rows 0-3, 12-15 at one slot and rows 4-11 at its
-// neighbour; a half-wave of the transposed read takes 8 consecutive rows x 32 bytes); this one has
-//   * q4_swz(r) ^ [4 <= r&15 < 12] a bijection of r & 15      -> the row reads are conflict-free,
-//   * q4_swz(r) >> 1 a bijection of r & 7                     -> the transposed reads are conflict-free.
 constexpr int kQ4BQ = 128;      // queries per workgroup
 constexpr int kQ4BK = 64;       // keys per step (two units of 32)
 constexpr int kQ4OffMeta = kD4Slots * kD4SlotBytes;
 constexpr int kQ4LdsBytes = kQ4OffMeta + kD4Slots * kQ4BK * 4;
 
-LWM_DEVICE int q4_swz(int row) {
-    const int r = row & 15;
-    return (((r & 7) << 1) | (r >> 3)) ^ ((r >= 4 && r < 12) ? 1 : 0);
-}
-LWM_DEVICE uint32_t q4_tile_off(int row, int slot) { return (uint32_t)(row * kRowBytes + ((slot ^ q4_swz(row)) << 4)); }
 
 // G = 0..15 = the gaps of Y(u), G = 16..47 = the gaps of X(u+1) (gap = behind that MFMA).  An MFMA holds the vector
 // issue for 8 of its 16 cycles, so a gap takes two plain VALU or one v_exp_f32 beside its LDS read.  F >= 3 (three
@@ -836,62 +990,6 @@ struct Q4Regs {
     bf16x8 fr[8];
 };
 
-#ifdef LWM_EMU
-// host form of v_mfma_f32_16x16x32_bf16 from its operand maps (scripts/micro/mfma_timing.hip prints the device's;
-// tests/test_gpu_dq16.py holds the device kernel to the oracle the emulated one meets)
-LWM_DEVICE f32x4 mfma_16x16x32(bf16x8 a, bf16x8 b, f32x4 c) {
-    emu::Wave& w = emu::g_blk->waves[emu::g_lane->tid >> 6];
-    const int l = emu::g_lane->tid & 63;
-    w.a[l] = a;
-    w.b[l] = b;
-    emu::wave_sync();
-    f32x4 d;
-    const int col = l & 15, g = l >> 4;
-    for (int j = 0; j < 4; ++j) {
-        const int row = 4 * g + j;
-        float s = c[j];
-        for (int k = 0; k < 32; ++k) s += (float)w.a[(k >> 3) * 16 + row][k & 7] * (float)w.b[(k >> 3) * 16 + col][k & 7];
-        d[j] = s;
-    }
-    emu::wave_sync();
-    return d;
-}
-LWM_DEVICE void q4_mfma_first(f32x4& d, bf16x8 a, bf16x8 b) { d = mfma_16x16x32(a, b, f32x4{0.0f, 0.0f, 0.0f, 0.0f}); }
-LWM_DEVICE void q4_mfma(f32x4& d, bf16x8 a, bf16x8 b) { d = mfma_16x16x32(a, b, d); }
-LWM_DEVICE void q4_mfma_c_first(f32x4& d, bf16x8 a, bf16x8 b, const f32x4& c) { d = mfma_16x16x32(a, b, c); }
-LWM_DEVICE void q4_mfma_o(f32x4& d, bf16x8 a, bf16x8 b) { d = mfma_16x16x32(a, b, d); }
-LWM_DEVICE void q4_mfma_o_first(f32x4& d, bf16x8 a, bf16x8 b) { d = mfma_16x16x32(a, b, f32x4{0.0f, 0.0f, 0.0f, 0.0f}); }
-LWM_DEVICE void q4_opaque(f32x4 (&)[2]) {}
-LWM_DEVICE void q4_settle_t(f32x4 (&)[4]) {}
-LWM_DEVICE void q4_settle_acc(f32x4 (&)[16]) {}
-#else
-// the statements of attn_fwd64.h / d4_mfma_* above on the 16x16 shape: S chains (B from the accumulator file), the
-// first MFMA of a dP chain (C = the -delta tuple, two wait states in front, see d4_mfma_p_first), dQ^T products
-LWM_DEVICE void q4_mfma_first(f32x4& d, bf16x8 a, bf16x8 b) {
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&v"(d) : "v"(a), "a"(b));
-}
-LWM_DEVICE void q4_mfma(f32x4& d, bf16x8 a, bf16x8 b) {
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "a"(b));
-}
-LWM_DEVICE void q4_mfma_c_first(f32x4& d, bf16x8 a, bf16x8 b, const f32x4& c) {
-    asm volatile("s_nop 1\n\tv_mfma_f32_16x16x32_bf16 %0, %1, %2, %3" : "=&v"(d) : "v"(a), "a"(b), "v"(c));
-}
-LWM_DEVICE void q4_mfma_o(f32x4& d, bf16x8 a, bf16x8 b) {
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(d) : "v"(a), "v"(b));
-}
-LWM_DEVICE void q4_mfma_o_first(f32x4& d, bf16x8 a, bf16x8 b) {
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&a"(d) : "v"(a), "v"(b));
-}
-// registers that hold the same value: hipcc must not know (it would keep one and copy it into a tuple in front of
-// every chain)
-LWM_DEVICE void q4_opaque(f32x4 (&x)[2]) { asm volatile("" : "+v"(x[0]), "+v"(x[1])); }
-LWM_DEVICE void q4_settle_t(f32x4 (&s)[4]) { asm volatile("s_nop 7\n\ts_nop 7" : "+v"(s[0]), "+v"(s[1]), "+v"(s[2]), "+v"(s[3])); }
-LWM_DEVICE void q4_settle_acc(f32x4 (&a)[16]) {
-    asm volatile("s_nop 7\n\ts_nop 7"
-                 : "+a"(a[0]), "+a"(a[1]), "+a"(a[2]), "+a"(a[3]), "+a"(a[4]), "+a"(a[5]), "+a"(a[6]), "+a"(a[7]), "+a"(a[8]),
-                   "+a"(a[9]), "+a"(a[10]), "+a"(a[11]), "+a"(a[12]), "+a"(a[13]), "+a"(a[14]), "+a"(a[15]));
-}
-#endif
 
 // fragment f of a unit (24 per unit, each feeds the MFMAs of the two query halves; 24.. = the first fragments of the
 // unit that follows):
