@@ -610,6 +610,45 @@ typedef struct LwmGemvW8Args {
 } LwmGemvW8Args;
 int lwm_gemv_fused_w8(const LwmGemvW8Args* args, void* stream);
 
+/* ------------------------------------------------------------------ 4-bit decode weights (lwm_version() >= 580)
+ * OCP MXFP4 copies of the same kernels: 4.25 bits per weight, 0.266 of the bf16 bytes and 0.515 of the 8-bit pack's.  A
+ * bf16 kernel W of shape [K, N] (K % 32 == 0, K <= 12288, N % 8 == 0) becomes
+ *   q      uint8 [K/4][N/8][16]       e2m1 codes (sign in bit 3; magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6 for the codes 0..7),
+ *                                     two per byte, K * N / 2 bytes.  NOT row-major: slot [k4][n8] holds rows
+ *                                     4 k4 .. 4 k4 + 3 of columns 8 n8 .. 8 n8 + 7; byte 4 j + b of the slot holds row
+ *                                     4 k4 + j, column 8 n8 + 2 b in its low nibble and column 8 n8 + 2 b + 1 in its high
+ *                                     nibble (the nibble order of the 4-bit KV cache).  W[k][n] is therefore the nibble
+ *                                     (n & 1) of byte ((k >> 2) * (N / 8) + (n >> 3)) * 16 + (k & 3) * 4 + ((n & 7) >> 1).
+ *                                     One 16-byte load of a GEMV lane brings four rows of its eight columns, and the 64
+ *                                     lanes of a wave read 1 KiB contiguous;
+ *   scale  uint8 [K/32][N]            one e8m0 byte b per MX block -- 32 consecutive rows of K of one column, the rows one
+ *                                     wave of the GEMV walks: the scale 2^(b - 127).
+ * Quantising one block: the rule of the 4-bit KV cache, not the saturating OCP one.  amax = max |w| over the block; s = the
+ * smallest power of two with amax / s <= 6, its exponent byte clamped to [1, 254], and byte 127 when amax == 0;
+ * q = e2m1(w / s), round to nearest, ties to the even code.  w / s is exact and |w / s| <= 6: nothing saturates; -0 keeps
+ * its sign.  Non-finite weights (Inf, NaN) are NOT supported, nor is a block whose amax exceeds 3.5 * 2^126.
+ * lwm_w4_quantise: one pass over w [K, N] bf16 -> q, scale_e8m0 and `rounded` [K, N] bf16 = bf16(e2m1(q) * s), the value
+ *   the codes stand for (`rounded` may be w itself: rounding in place).  Every pointer 16-byte aligned.  No atomics: the
+ *   same input gives the same bits.
+ * lwm_gemv_fused_w4: lwm_gemv_fused_bf16 with w[i] = the codes and w_scale[i] = the scale bytes of kernel i; every other
+ *   field means what it means in LwmGemvArgs (rows <= 4, K % 32 == 0, K <= 12288; N[i] % 8 == 0; workspace of the sum of
+ *   lwm_gemv_workspace_bytes(rows, K, N[i]) bytes), and the refusals are those of lwm_gemv_fused_w8.  Same K partition,
+ *   same order of every sum as the bf16 entry; the block's scale multiplies the sum over the block's 32 rows once.
+ *   Exactness domain: e2m1(q) * s has 2 significant bits and is a bf16 value whenever it is a normal number, and with
+ *   power-of-two scales and neither overflow nor underflow in the partial sums (scales between 2^-40 and 2^40 and
+ *   activations of ordinary size are well inside) the results -- outputs and workspace partials -- are BIT FOR BIT those
+ *   of lwm_gemv_fused_bf16 on the `rounded` weights. */
+int lwm_w4_quantise(const void* w, void* q, void* scale_e8m0, void* rounded, int32_t K, int32_t N, void* stream);
+typedef struct LwmGemvW4Args {
+    const void* x; int64_t ldx; int32_t nmat; int32_t rows, K;
+    const void* w[3]; const uint8_t* w_scale[3]; void* y[3]; int64_t ldy[3]; float* y_f32[3]; int32_t N[3];
+    void* workspace;
+    const void* norm_weight; const float* ss_in; int32_t ss_n; float eps;
+    const void* residual[3]; int64_t ldres[3];
+    float* ss_out;
+} LwmGemvW4Args;
+int lwm_gemv_fused_w4(const LwmGemvW4Args* args, void* stream);
+
 /* ------------------------------------------------------------------ decode projections for 1..32 rows (lwm_version() >= 560)
  * The same products on the matrix pipe (v_mfma_f32_16x16x32_bf16) for batches past the GEMV's four rows: W is still read
  * once.  Every field of LwmGemvArgs / LwmGemvW8Args means what it means for lwm_gemv_fused_bf16 / lwm_gemv_fused_w8, with
@@ -793,7 +832,7 @@ int lwm_version(void);
 /* sizeof(LwmAttnArgs) (which = 0) / sizeof(LwmConvArgs) (1) / sizeof(LwmRingArgs) (2) / sizeof(LwmGemvArgs) (3) /
  * sizeof(LwmSampleArgs) (4) / sizeof(LwmKv8DecodeArgs) (5) / sizeof(LwmKv8PrefillArgs) (6) / sizeof(LwmAdamWArgs) (7) as
  * sizeof(LwmAdamWTensor) (8: an element of a device table that the caller lays out) / sizeof(LwmGemvW8Args) (9) /
- * sizeof(LwmKv4DecodeArgs) (10) as
+ * sizeof(LwmKv4DecodeArgs) (10) / sizeof(LwmGemvW4Args) (11) as
  * compiled into the library:
  * lets a foreign-language binding verify its struct mirror at load time. */
 int lwm_sizeof(int which);

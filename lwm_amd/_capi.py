@@ -98,6 +98,11 @@ class LwmGemvW8Args(C.Structure):
     ]
 
 
+class LwmGemvW4Args(C.Structure):
+    """LwmGemvArgs with w[i] as e2m1 nibble pairs plus their e8m0 scale-byte tables"""
+    _fields_ = LwmGemvW8Args._fields_
+
+
 class LwmKv8DecodeArgs(C.Structure):
     _fields_ = [
         ("q", LwmTensor4), ("k", C.c_void_p), ("v", C.c_void_p),
@@ -264,6 +269,8 @@ PROTOTYPES = {
     "lwm_gemv_fused_bf16": (C.c_int, [C.POINTER(LwmGemvArgs), C.c_void_p]),
     "lwm_w8_quantise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "lwm_gemv_fused_w8": (C.c_int, [C.POINTER(LwmGemvW8Args), C.c_void_p]),
+    "lwm_w4_quantise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "lwm_gemv_fused_w4": (C.c_int, [C.POINTER(LwmGemvW4Args), C.c_void_p]),
     "lwm_gemm_rows_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "lwm_gemm_rows_fused_bf16": (C.c_int, [C.POINTER(LwmGemvArgs), C.c_void_p]),
     "lwm_gemm_rows_fused_w8": (C.c_int, [C.POINTER(LwmGemvW8Args), C.c_void_p]),
@@ -295,7 +302,7 @@ def bind(lib):
         fn.argtypes = args
     for which, cls in ((0, LwmAttnArgs), (1, LwmConvArgs), (2, LwmRingArgs), (4, LwmSampleArgs), (5, LwmKv8DecodeArgs),
                        (6, LwmKv8PrefillArgs), (7, LwmAdamWArgs), (8, LwmAdamWTensor), (9, LwmGemvW8Args),
-                       (10, LwmKv4DecodeArgs)):
+                       (10, LwmKv4DecodeArgs), (11, LwmGemvW4Args)):
         if lib.lwm_sizeof(which) != C.sizeof(cls):
             raise ImportError(f"{cls.__name__}: ctypes mirror is {C.sizeof(cls)} bytes, library has "
                               f"{lib.lwm_sizeof(which)} (include/lwm_hip.h and lwm_amd/_capi.py out of step)")

@@ -56,10 +56,16 @@ def sampler_kwargs(model, seed, generator):
 def apply_decode_weights(model):
     """LWM_DECODE_WEIGHTS=fp8: once the weights are loaded, round the projection kernels in place to their e4m3 values and
     keep 8-bit packs of them for the one-token steps (model.quantize_decode_weights: 0.516 of the weight bytes per token,
-    +0.516x weight memory; bf16 models on one rank).  'bf16' or unset: nothing happens."""
+    +0.516x weight memory; bf16 models on one rank).  LWM_DECODE_WEIGHTS=fp4: the same with MXFP4 packs (0.266 of the bytes,
+    +0.266x weight memory; 4-bit rounding moves the logits -- check quality on the model in use).  'bf16' or unset: nothing
+    happens."""
     mode = os.environ.get("LWM_DECODE_WEIGHTS", "").lower()
-    if mode not in ("", "bf16", "fp8"):
-        raise SystemExit(f"LWM_DECODE_WEIGHTS={mode!r}: 'fp8', 'bf16' (the default) or unset")
+    if mode not in ("", "bf16", "fp8", "fp4"):
+        raise SystemExit(f"LWM_DECODE_WEIGHTS={mode!r}: 'fp8', 'bf16' (the default), 'fp4' or unset")
+    if mode == "fp4":
+        model.quantize_decode_weights("fp4")
+        note("LWM_DECODE_WEIGHTS=fp4: projection kernels rounded in place to MXFP4 values; one-token steps of up to 4 rows stream "
+             "the 4-bit packs")
     if mode == "fp8":
         model.quantize_decode_weights("fp8")
         note("LWM_DECODE_WEIGHTS=fp8: projection kernels rounded in place to e4m3 values; one-token steps stream the 8-bit packs")

@@ -20,8 +20,8 @@
 //         (lwm/llama.py:719, :737), and the partial sums of squares of y for the next norm (ss_out).
 // R <= 4 rows, N % 8 == 0, K % 32 == 0, K <= 12288 (LWM-7B: 4096, 11008, 32000 all qualify).
 //
-// Shared with the other weight-streaming kernels: gemv_body<W, R> is the body of gemv_w8.h's kernel too (W = the weight
-// format: GemvBf16Format here, GemvW8Format there).  gemm_rows.h restates the tile lookup (gemv_tile) and the RMSNorm on
+// Shared with the other weight-streaming kernels: gemv_body<W, R> is the body of gemv_w8.h's and gemv_w4.h's kernels too
+// (W = the weight format: GemvBf16Format here, GemvW8Format and GemvW4Format there).  gemm_rows.h restates the tile lookup (gemv_tile) and the RMSNorm on
 // load (gemv_row_rstd, gemv_norm) inside its MFMA body and must stay equal to them; all three kernels feed
 // gemv_reduce_kernel the same partials layout.
 #pragma once
@@ -82,17 +82,22 @@ LWM_DEVICE float gemv_row_rstd(const GemvParams& p, int r, int lane) {
 // RMSNorm on load: the arithmetic of rmsnorm_fwd_kernel
 LWM_DEVICE float gemv_norm(float x, float rstd, float g) { return (float)(bf16_t)((float)(bf16_t)(x * rstd) * g); }
 
-// The bf16 weight format of gemv_body (the e4m3 one: GemvW8Format in gemv_w8.h).  A format names the kernel's parameters,
-// one lane's load of 8 columns of a row, its accumulators for them and the FMA step of one row of W against x[r, i] of every row r, a scalar out of xv; quad(acc, j) gives
-// columns 4j..4j+3 of the accumulators.  kScaled: scale() loads the K group's scales of columns 4j..4j+3.
+// The bf16 weight format of gemv_body (the e4m3 one: GemvW8Format in gemv_w8.h; the e2m1 one: GemvW4Format in gemv_w4.h).
+// A format names the kernel's parameters, one lane's load of 8 columns of kRows consecutive rows (at offset(k, n, N)
+// elements into the matrix), its accumulators for them and the FMA step of those rows of W against x[r, i..i+kRows) of
+// every row r, scalars out of xv; quad(acc, j) gives columns 4j..4j+3 of the accumulators.  kScaled: scale() loads the K
+// group's scales of columns 4j..4j+3.  kWaveScaled: the wave's 32 rows share one scale per column -- wave_scale() loads
+// the 8 of the lane's columns (table offset `at`) and scale_wave() multiplies a finished wave sum by them.
 struct GemvBf16Format {
     using Params = GemvParams;
     using Elem = bf16_t;
     using Load = u32x4;
     using Acc = float[8];
-    static constexpr bool kScaled = false;
+    static constexpr bool kScaled = false, kWaveScaled = false;
+    static constexpr int kRows = 1;
     LWM_DEVICE static const GemvParams& g(const Params& p) { return p; }
     LWM_DEVICE static const Elem* matrix(const Params& p, int mi) { return p.w[mi]; }
+    LWM_DEVICE static int64_t offset(int k, int n, int N) { return (int64_t)k * N + n; }
     LWM_DEVICE static Load load(const Elem* at) { return global_load_b128(at); }
     LWM_DEVICE static void zero(Acc& a) {
         for (int j = 0; j < 8; ++j) a[j] = 0.0f;
@@ -137,18 +142,22 @@ LWM_DEVICE void gemv_body(const typename W::Params& pp) {
     }
     typename W::Acc acc[R];
     for (int r = 0; r < R; ++r) W::zero(acc[r]);
-    const typename W::Elem* wp = W::matrix(pp, mi) + n;
+    const typename W::Elem* wp = W::matrix(pp, mi);
+    u32x2 wsc = {};                                // the scales of the wave's rows, where the format has them
+    if constexpr (W::kWaveScaled) wsc = W::wave_scale(pp, mi, (int64_t)((k0 < p.K ? k0 : p.K - kGemvRPW) / kGemvRPW) * N + n);
 #pragma unroll
-    for (int i0 = 0; i0 < kGemvRPW; i0 += 8) {
+    for (int i0 = 0; i0 < kGemvRPW; i0 += 8 * W::kRows) {
         typename W::Load wv[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
-            const int k = k0 + i0 + u;
-            wv[u] = W::load(wp + (int64_t)(k < p.K ? k : p.K - 1) * N);        // rows past K meet x = 0
+            const int k = k0 + i0 + u * W::kRows;
+            wv[u] = W::load(wp + W::offset(k < p.K ? k : p.K - W::kRows, n, N));       // rows past K meet x = 0
         }
 #pragma unroll
-        for (int u = 0; u < 8; ++u) W::fma(acc, wv[u], xv, i0 + u);
+        for (int u = 0; u < 8; ++u) W::fma(acc, wv[u], xv, i0 + u * W::kRows);
     }
+    if constexpr (W::kWaveScaled)
+        for (int r = 0; r < R; ++r) W::scale_wave(acc[r], wsc);    // once per wave sum: the scales are powers of two
     // waves 1..3 hand their sums to wave 0 through LDS; wave 0 adds them in wave order
     if (wave > 0) {
         for (int r = 0; r < R; ++r) {

@@ -41,9 +41,11 @@ struct GemvW8Format {
     using Elem = uint8_t;
     using Load = u32x2;
     using Acc = f32x2[4];
-    static constexpr bool kScaled = true;
+    static constexpr bool kScaled = true, kWaveScaled = false;
+    static constexpr int kRows = 1;
     LWM_DEVICE static const GemvParams& g(const Params& p) { return p.g; }
     LWM_DEVICE static const Elem* matrix(const Params& p, int mi) { return p.q[mi]; }
+    LWM_DEVICE static int64_t offset(int k, int n, int N) { return (int64_t)k * N + n; }
     LWM_DEVICE static Load load(const Elem* at) { return global_load_b64(at); }
     LWM_DEVICE static void zero(Acc& a) {
         for (int j = 0; j < 4; ++j) a[j] = f32x2{0.0f, 0.0f};

@@ -382,6 +382,7 @@ class LLaMAForCausalLM(torch.nn.Module):
         self.lm_head = _dense(cfg.hidden_size, cfg.vocab_size, cfg.initializer_range, dtype)
         self._freqs = None
         self._w8 = None            # quantize_decode_weights("fp8"): {parameter name: lwm_amd.w8.W8Kernel}
+        self._w4 = None            # quantize_decode_weights("fp4"): {parameter name: lwm_amd.w4.W4Kernel}; _w8 stays None
         self._decode_rows = None   # decode_rows: None = LWM_DECODE_ROWS
 
     def _table(self, device):
@@ -483,35 +484,52 @@ class LLaMAForCausalLM(torch.nn.Module):
         heads at those row counts stream the packs (lwm_gemv_fused_w8; lwm_gemm_rows_fused_w8 above 4 rows) -- bit for bit what the bf16 GEMV gives on the rounded parameters, from 0.516 of the bytes.
         The bf16 parameters stay: the weights take 1.516x their memory.  A pack whose parameter changes afterwards is
         refused at its next use (RuntimeError): quantise again.  mode="bf16" / None = drop_decode_weights().
+        mode="fp4": the same with 4-bit packs (include/lwm_hip.h "4-bit decode weights", lwm_amd/w4.py): the kernels are ROUNDED
+        IN PLACE to their MXFP4 values (e2m1 codes, one power-of-two scale per 32 rows of K and column) and the fused one-token
+        step and the heads' f32 logits at up to 4 rows stream the packs (lwm_gemv_fused_w4) -- bit for bit what the bf16 GEMV
+        gives on the rounded parameters, from 0.266 of the bytes; the weights take 1.266x their memory.  There is no 4-bit
+        body for more than 4 rows: where decode_rows is set, steps of 5.. rows run lwm_gemm_rows_fused_bf16 over the bf16
+        parameters -- those ARE the rounded model, so that route computes the same model and only saves no bytes.  4-bit
+        round-to-nearest moves a model's logits far more than the 8-bit packs do: check quality on the model in use.
+        A later "fp8" replaces the 4-bit packs (rounding the already rounded kernels again) and the other way round; only one
+        kind of pack is held at a time.
         bf16 models on one rank."""
         if mode in (None, "bf16"):
             return self.drop_decode_weights()
-        if mode != "fp8":
-            raise ValueError(f"quantize_decode_weights({mode!r}): 'fp8', or 'bf16' / None (drop_decode_weights)")
+        if mode not in ("fp8", "fp4"):
+            raise ValueError(f"quantize_decode_weights({mode!r}): 'fp8', 'fp4', or 'bf16' / None (drop_decode_weights)")
+        bits = "8-bit" if mode == "fp8" else "4-bit"
         if self.dtype != torch.bfloat16:
-            raise NotImplementedError("quantize_decode_weights('fp8') with a float32 model: the 8-bit packs are made from bf16 "
+            raise NotImplementedError(f"quantize_decode_weights({mode!r}) with a float32 model: the {bits} packs are made from bf16 "
                                       "kernels and the GEMV that streams them takes bf16 activations (--dtype=bf16, or bf16 weights)")
         if sp_size_rank("sp")[0] > 1:
-            raise NotImplementedError("quantize_decode_weights('fp8') with sp > 1: the fused one-token step runs on one rank "
+            raise NotImplementedError(f"quantize_decode_weights({mode!r}) with sp > 1: the fused one-token step runs on one rank "
                                       "(one rank, or bf16 decode weights)")
-        from .w8 import quantise_weight
+        if mode == "fp8":
+            from .w8 import quantise_weight
+        else:
+            from .w4 import quantise_weight
         packs = {}
         for name, p in self._decode_weight_params():
             try:
                 packs[name] = quantise_weight(p)
             except ValueError as e:
-                raise ValueError(f"quantize_decode_weights('fp8'): {name}: {e}") from None
-        self._w8 = packs
+                raise ValueError(f"quantize_decode_weights({mode!r}): {name}: {e}") from None
+        self._w8, self._w4 = (packs, None) if mode == "fp8" else (None, packs)
         return self
 
     def drop_decode_weights(self):
         """Back to bf16 weight streaming.  The parameters stay as they are (rounded, if they were quantised)."""
-        self._w8 = None
+        self._w8 = self._w4 = None
         return self
 
     def _w8_packs(self, names, kernels):
         """the packs of `kernels`, each checked against its parameter as it is NOW"""
         return [self._w8[n].check(k, n) for n, k in zip(names, kernels)]
+
+    def _w4_packs(self, names, kernels):
+        """the same for the 4-bit packs"""
+        return [self._w4[n].check(k, n) for n, k in zip(names, kernels)]
 
     def _decode_layers_fused(self, x, fc, attention_mask, position_ids, cache):
         """The blocks of a cached one-token step (lwm/llama.py:704-744 with q_len = 1) with each RMSNorm folded into the
@@ -526,6 +544,10 @@ class LLaMAForCausalLM(torch.nn.Module):
             fused_w8 = w8.gemv_fused_w8 if B <= 4 else w8.gemm_rows_fused_w8
             names = {id(p): n for n, p in self._decode_weight_params()}
             gemv_fused = lambda x, ks, **kw: fused_w8(x, self._w8_packs([names[id(k)] for k in ks], ks), **kw)    # noqa: E731
+        elif getattr(self, "_w4", None) is not None and B <= 4:    # ... over the 4-bit packs (above 4 rows: the rounded bf16 parameters)
+            from . import w4
+            names = {id(p): n for n, p in self._decode_weight_params()}
+            gemv_fused = lambda x, ks, **kw: w4.gemv_fused_w4(x, self._w4_packs([names[id(k)] for k in ks], ks), **kw)    # noqa: E731
         H, D = self.cfg.num_attention_heads, d // self.cfg.num_attention_heads
         x2 = x.reshape(B, d)
         ss = torch.zeros(B, 32, dtype=torch.float32, device=x.device)
@@ -707,6 +729,21 @@ def w8_head_logits(model, h, head):
     return y.reshape(*h.shape[:-1], y.shape[-1])
 
 
+def w4_head_logits(model, h, head):
+    """w8_head_logits for the 4-bit packs: at most four rows (more rows take the bf16 head, the rounded parameter)"""
+    packs = getattr(model, "_w4", None)
+    if packs is None:
+        return None
+    same = lambda p: p is head or (p.data_ptr() == head.data_ptr() and p.shape == head.shape and p.stride() == head.stride())
+    name = next((n for n in packs if "." not in n and same(getattr(model, n))), None)
+    rows = h.numel() // h.shape[-1]
+    if name is None or rows > 4 or not h.is_cuda or h.dtype != torch.bfloat16 or torch.is_grad_enabled():
+        return None
+    from . import w4
+    (y,) = w4.gemv_fused_w4(h.reshape(rows, h.shape[-1]), model._w4_packs((name,), (head,)), out_dtype=torch.float32)
+    return y.reshape(*h.shape[:-1], y.shape[-1])
+
+
 def model_decode_rows(model):
     """model.decode_rows; LWM_DECODE_ROWS for a stand-in model without the attribute"""
     try:
@@ -716,9 +753,11 @@ def model_decode_rows(model):
 
 
 def head_logits(model, h, head):
-    """f32 logits of `head`: through its 8-bit pack where the model has one, else `dense(h, head, torch.float32)` (the GEMV
-    for <= 4 rows, lwm_gemm_rows_fused_bf16 up to model.decode_rows, the library beyond)"""
+    """f32 logits of `head`: through its 8-bit or 4-bit pack where the model has one, else `dense(h, head, torch.float32)`
+    (the GEMV for <= 4 rows, lwm_gemm_rows_fused_bf16 up to model.decode_rows, the library beyond)"""
     y = w8_head_logits(model, h, head)
+    if y is None:
+        y = w4_head_logits(model, h, head)
     if y is not None:
         return y
     with decode_rows_scope(model_decode_rows(model)):
