@@ -685,13 +685,31 @@ int lwm_gemm_rows_fused_w8(const LwmGemvW8Args* args, void* stream);
 int lwm_softmax_ce_bf16(const void* logits, const int32_t* target, const float* weight, float* nll,
                         int32_t* correct, void* dlogits, int64_t rows, int32_t V, void* stream);
 
-/* ------------------------------------------------------------------ token sampler (lwm_version() >= 510)
+/* ------------------------------------------------------------------ token sampler (lwm_version() >= 510; top_p: >= 590)
  * One decode step's choice of the next token, per output row b (lwm/vision_llama.py:476-560 _sample_vision;
  * lwm/vision_chat.py:201-213 generate(do_sample=True)), in one launch:
  *   logit   cfg_scale == NULL: row b of `logits`; else rows [0,B) are conditional, [B,2B) unconditional (rows = 2B) and
  *           the logit is u + s*(c - u) with s = cfg_scale[b], three f32 roundings (no fused multiply-add);
  *   greedy  temperature == 0: argmax, lowest index on ties;
  *   filter  0 < top_k < V: keep every entry >= the top_k-th largest of logit / temperature (ties at it all stay);
+ *   top-p   0 < top_p < 1 (lwm_version() >= 590; 0 or >= 1: no filter; negative or NaN: LWM_EINVAL), after top-k and
+ *           normalised over its survivors K, the order of HF's warpers.  With s_j = logit_j / temperature (f32),
+ *           w_j = exp(s_j - max_K s), Z = sum of w over K and M(j) = the sum of w_i over i in K with s_i > s_j (the mass
+ *           strictly above j):   entry j stays iff j is in K and M(j) < top_p * Z.
+ *           The largest entry always stays (M = 0); entries of equal s stay or go together; a -inf entry never stays
+ *           while a finite one exists; greedy ignores top_p as it ignores top_k.  This is FlaxTopPLogitsWarper (cumsum <
+ *           top_p rolled by one, min_tokens_to_keep = 1) and torch's TopPLogitsWarper, except that a group of equal
+ *           values at the boundary is not split.  A row with a +inf or NaN logit, or without a finite one, has no such
+ *           mass: K stays whole.
+ *           Arithmetic: the kept set S is a prefix of the descending order with S-(eps) <= S <= S+(eps), S+-(eps) =
+ *           {j in K: M(j) < top_p * Z * (1 +- eps)} in exact arithmetic on the f32 s, eps = 2^-20 (9.6e-7).  Derivation:
+ *           s_j - max is taken in f64, the f32 exponential of its f32 rounding is corrected by the rounding's remainder
+ *           in f64 (second-order term < 2e-11) and the weight is kept as an f32, so it carries the exponential's own
+ *           error, 2 f32 ulps = 2^-22 at most, and one rounding, 2^-24: delta = 1.25 * 2^-22; weights of subnormal size
+ *           add less than V * 2^-126 in all, against M >= 1 for every entry below the largest; the sums are fixed trees
+ *           of f64 additions with chains of at most V / 1024 + 160 links (< 2^-33 relative for any V) and top_p * Z is an
+ *           f64 product.  M and Z each move by at most delta, so every entry with M outside top_p * Z * (1 +- 2 * delta),
+ *           2 * delta = 0.625 * 2^-20, is decided as in exact arithmetic; eps rounds that up to a power of two.
  *   draw    argmax over the kept entries of logit / temperature + g_j, lowest index on ties (Gumbel-max), with
  *           g = -log(-log(u)), u = ((x >> 9) + 0.5) * 2^-23 and x word (j % 4) of Philox4x32-10 (key = seed, counter =
  *           (j / 4, b, step, 0));
@@ -701,7 +719,7 @@ int lwm_softmax_ce_bf16(const void* logits, const int32_t* target, const float* 
  *   done    done != NULL (u8 [B]): a row whose done[b] is set emits pad; then done[b] |= (token == eos) (eos < 0: none);
  *   outputs tokens[c*B + b] for c < copies (int64: the next step's input ids, both CFG halves with copies = 2) and / or
  *           seq[b*seq_ld + step] when 0 <= step < seq_cols (int64).
- * The token depends on (logits, cfg, temperature, top_k, seed, b, step) only.  Any V in [1, 2^30]; logits rows ld >= V
+ * The token depends on (logits, cfg, temperature, top_k, top_p, seed, b, step) only.  Any V in [1, 2^30]; logits rows ld >= V
  * apart (elements); pointers 4-byte (logits, cfg_scale, step_dev) / 8-byte (tokens, seq) aligned. */
 typedef struct LwmSampleArgs {
     const float* logits;       /* [rows][ld] f32 */
@@ -721,6 +739,7 @@ typedef struct LwmSampleArgs {
     int64_t* seq;              /* [B][seq_ld] or NULL */
     int64_t seq_ld;
     int32_t seq_cols;
+    float top_p;               /* lwm_version() >= 590, in what was padding: sizeof is unchanged and 0 = no filter */
 } LwmSampleArgs;
 int lwm_sample_tokens(const LwmSampleArgs* args, void* stream);
 

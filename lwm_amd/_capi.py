@@ -145,7 +145,7 @@ class LwmSampleArgs(C.Structure):
         ("step_dev", C.c_void_p), ("step_base", C.c_int32), ("step", C.c_int32),
         ("force_period", C.c_int32), ("force_token", C.c_int32), ("done", C.c_void_p), ("eos", C.c_int64),
         ("pad", C.c_int64), ("tokens", C.c_void_p), ("copies", C.c_int32), ("seq", C.c_void_p), ("seq_ld", C.c_int64),
-        ("seq_cols", C.c_int32),
+        ("seq_cols", C.c_int32), ("top_p", C.c_float),
     ]
 
 

@@ -22,6 +22,19 @@ def note(msg):
     print(f"[lwm_amd.cli] {msg}", file=sys.stderr, flush=True)
 
 
+def parse_top_p(text):
+    """LWM_TOP_P -> None (unset or empty) or a float in (0, 1]; anything else ends the run, naming the variable"""
+    if not text:
+        return None
+    try:
+        p = float(text)
+    except ValueError:
+        p = float("nan")
+    if not 0.0 < p <= 1.0:
+        raise SystemExit(f"LWM_TOP_P={text!r}: a nucleus mass p with 0 < p <= 1 (1 = no filter), or unset")
+    return p
+
+
 def sampler_kwargs(model, seed, generator):
     """How the entry points draw tokens.  Default: the torch sampler driven by `generator` (eager one-token steps).
     LWM_DECODE_GRAPH=1: every token drawn on the device from the Philox stream of --seed (lwm_amd.ops.sample_tokens),
@@ -31,8 +44,10 @@ def sampler_kwargs(model, seed, generator):
     bf16 models on one rank), with either sampler.  LWM_KV_CACHE=fp4: the 4-bit MXFP4 KV cache (generate(kv_dtype="fp4"):
     0.27 of the cache bytes; the same conditions, and no LWM_PREFILL_CHUNK with it).
     LWM_PREFILL_CHUNK=N: the prompt goes through the layers in blocks of N tokens (generate(prefill_chunk=N): the
-    prefill's activations are bounded by N; with the 8-bit cache every block after the first attends over quantised rows)."""
-    kv = os.environ.get("LWM_KV_CACHE", "").lower()
+    prefill's activations are bounded by N; with the 8-bit cache every block after the first attends over quantised rows).
+    LWM_TOP_P=p, 0 < p <= 1: nucleus sampling after temperature and top-k (generate(top_p=p)), with either sampler; the
+    reference's flag set has no top_p, so it is an environment variable.  Unset or empty: nothing changes."""
+    kv =os.environ.get("LWM_KV_CACHE", "").lower()
     if kv not in ("", "bf16", "fp8", "fp4"):
         raise SystemExit(f"LWM_KV_CACHE={kv!r}: 'fp4', 'fp8', 'bf16' (the default) or unset")
     extra = dict(kv_dtype=kv) if kv in ("fp8", "fp4") else {}
@@ -44,6 +59,9 @@ def sampler_kwargs(model, seed, generator):
             extra["prefill_chunk"] = 0
         if extra["prefill_chunk"] < 1:
             raise SystemExit(f"LWM_PREFILL_CHUNK={chunk!r}: a block length >= 1 (tokens per prefill call), or unset")
+    top_p = parse_top_p(os.environ.get("LWM_TOP_P", ""))
+    if top_p is not None:
+        extra["top_p"] = top_p
     if os.environ.get("LWM_DECODE_GRAPH", "0") != "1":
         return dict(generator=generator, **extra)
     graph = model.dtype == torch.bfloat16

@@ -885,6 +885,7 @@ int lwm_sample_tokens(const LwmSampleArgs* a, void* stream) {
     if (a->rows < 1 || a->ld < a->V) return fail(LWM_EINVAL, "%s: rows = %ld, ld = %ld (need rows >= 1, ld >= V)", "sample_tokens", a->rows, (long)a->ld);
     if (a->top_k < 0) return fail(LWM_EINVAL, "%s: top_k = %ld < 0", "sample_tokens", a->top_k);
     if (!(a->temperature >= 0.0f)) return fail(LWM_EINVAL, "%s", "sample_tokens: temperature must be >= 0 (0 = greedy)");
+    if (!(a->top_p >= 0.0f)) return fail(LWM_EINVAL, "%s", "sample_tokens: top_p must be >= 0 (0 or >= 1 = no filter)");
     if (a->cfg_scale && (a->rows & 1))
         return fail(LWM_EINVAL, "%s: rows = %ld is odd (cfg_scale: conditional rows, then as many unconditional ones)", "sample_tokens", a->rows);
     const int32_t B = a->cfg_scale ? a->rows / 2 : a->rows;
@@ -898,13 +899,17 @@ int lwm_sample_tokens(const LwmSampleArgs* a, void* stream) {
         return fail(LWM_EINVAL, "%s", "sample_tokens: misaligned pointer (logits, cfg_scale, step_dev: 4 bytes; tokens, seq: 8)");
     SampleParams p;
     p.logits = a->logits; p.ld = a->ld; p.V = a->V; p.B = B; p.cfg = a->cfg_scale != nullptr; p.cfg_scale = a->cfg_scale;
-    p.temperature = a->temperature; p.top_k = a->top_k;
+    p.temperature = a->temperature; p.top_k = a->top_k; p.top_p = a->top_p;
     p.key0 = (uint32_t)a->seed; p.key1 = (uint32_t)(a->seed >> 32);
     p.step_dev = a->step_dev; p.step_base = a->step_base; p.step = a->step;
     p.force_period = a->force_period; p.force_token = a->force_token;
     p.done = a->done; p.eos = a->eos; p.pad = a->pad;
     p.tokens = a->tokens; p.copies = a->copies;
     p.seq = a->seq; p.seq_ld = a->seq_ld; p.seq_cols = a->seq_cols;
+    // the top-p phase is a kernel of its own (with its mass tables in LDS): a launch with top-p off runs the code it ran
+    // before the phase existed
+    if (a->temperature > 0.0f && a->top_p > 0.0f && a->top_p < 1.0f)
+        return launch("sample_tokens", sample_top_p_kernel, B, kSampleThreads, kSampleTopPLdsBytes, stream, p);
     return launch("sample_tokens", sample_kernel, B, kSampleThreads, kSampleLdsBytes, stream, p);
 }
 
@@ -963,7 +968,7 @@ int lwm_adamw_step(const LwmAdamWArgs* a, void* stream) {
 int lwm_adamw_chunk(void) { return lwm::kAdamWChunk; }
 
 const char* lwm_last_error(void) { return lwm::g_err; }
-int lwm_version(void) { return 580; }
+int lwm_version(void) { return 590; }
 int lwm_sizeof(int which) {
     return which == 0 ? (int)sizeof(LwmAttnArgs) : which == 1 ? (int)sizeof(LwmConvArgs) : which == 2 ? (int)sizeof(LwmRingArgs) : which == 3 ? (int)sizeof(LwmGemvArgs) : which == 4 ? (int)sizeof(LwmSampleArgs) : which == 5 ? (int)sizeof(LwmKv8DecodeArgs) : which == 6 ? (int)sizeof(LwmKv8PrefillArgs) : which == 7 ? (int)sizeof(LwmAdamWArgs) : which == 8 ? (int)sizeof(LwmAdamWTensor) : which == 9 ? (int)sizeof(LwmGemvW8Args) : which == 10 ? (int)sizeof(LwmKv4DecodeArgs) : which == 11 ? (int)sizeof(LwmGemvW4Args) : -1;
 }

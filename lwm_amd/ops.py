@@ -645,15 +645,29 @@ def vq_gather(codebook, idx, z=None):
     return out
 
 
+def _check_top_p(top_p, who):
+    """top_p of the samplers: None or 1.0 = off (-> 0.0, the C struct's "no filter"), 0 < top_p < 1 -> that float;
+    anything else, NaN included, is refused by name"""
+    if top_p is None:
+        return 0.0
+    top_p = float(top_p)
+    if not 0.0 < top_p <= 1.0:
+        raise ValueError(f"{who}: top_p = {top_p!r} must lie in (0, 1] (None or 1.0 = no nucleus filter)")
+    return 0.0 if top_p == 1.0 else max(top_p, 2.0 ** -126)       # (the struct's float: never rounded to its 0 = off)
+
+
 def sample_tokens(logits, *, temperature, top_k, seed, step_dev=None, step=0, step_base=0, cfg_scale=None, force_period=0,
-                  force_token=0, done=None, eos=None, pad=0, tokens_out=None, copies=1, seq_out=None):
+                  force_token=0, done=None, eos=None, pad=0, tokens_out=None, copies=1, seq_out=None, top_p=None):
     """One decode step's next token per output row, drawn on the device (lwm_sample_tokens, csrc/sample.h): guidance
     over (2B, V) logits when cfg_scale (B,) is given (conditional rows first), temperature (0 = greedy), top-k (0 =
-    none), a Gumbel-max draw from the Philox stream of (seed, entry, row, step).  `step` is read from the one-element
+    none), top-p (None or 1.0 = none; 0 < top_p < 1: the nucleus rule of include/lwm_hip.h over the top-k survivors --
+    an entry stays iff the softmax mass strictly above it is below top_p; anything outside (0, 1] is a ValueError), a
+    Gumbel-max draw from the Philox stream of (seed, entry, row, step).  `step` is read from the one-element
     int32 device tensor step_dev (minus step_base) or taken from the host value.  force_period / force_token, done ((B,)
     uint8) / eos / pad, the int64 outputs tokens_out ((copies * B, 1): the next step's input ids) and seq_out ((B, n):
     column `step`) as include/lwm_hip.h documents.  Returns tokens_out -- allocated when not given; a call that is handed
     every output allocates nothing and can be captured in a hipGraph."""
+    top_p = _check_top_p(top_p, "sample_tokens")
     if not logits.is_cuda or logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1:
         raise ValueError("sample_tokens: logits must be a (rows, V) f32 device tensor with contiguous rows")
     rows, V = logits.shape
@@ -671,7 +685,7 @@ def sample_tokens(logits, *, temperature, top_k, seed, step_dev=None, step=0, st
     a = _capi.LwmSampleArgs()
     a.logits, a.ld, a.rows, a.V = logits.data_ptr(), logits.stride(0), rows, V
     a.cfg_scale = dev_ptr(cfg_scale, "cfg_scale", torch.float32, B)
-    a.temperature, a.top_k = float(temperature), int(top_k or 0)
+    a.temperature, a.top_k, a.top_p = float(temperature), int(top_k or 0), top_p
     a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     a.step_dev = dev_ptr(step_dev, "step_dev", torch.int32, 1)
     a.step_base, a.step = int(step_base), int(step)

@@ -119,9 +119,11 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
         return h[:, -1], (pos + 1).contiguous()
 
     @staticmethod
-    def _pick(logits, temperature, top_k, do_sample, gen):
-        """FlaxTemperatureLogitsWarper / FlaxTopKLogitsWarper + categorical sampling (greedy when
-        do_sample is False or temperature == 0)."""
+    def _pick(logits, temperature, top_k, do_sample, gen, top_p=0.0):
+        """FlaxTemperatureLogitsWarper / FlaxTopKLogitsWarper / FlaxTopPLogitsWarper + categorical sampling (greedy when
+        do_sample is False or temperature == 0).  top_p (0 = off) is the nucleus rule of include/lwm_hip.h, the one the
+        device sampler applies: over the top-k survivors an entry stays iff the softmax mass strictly above it is below
+        top_p; entries of equal value stay or go together."""
         logits = logits.float()
         if not do_sample or temperature == 0:
             return logits.argmax(-1, keepdim=True)
@@ -129,6 +131,17 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
         if top_k and 0 < top_k < logits.shape[-1]:
             kth = logits.topk(int(top_k), dim=-1).values[..., -1:]
             logits = logits.masked_fill(logits < kth, float("-inf"))
+        if 0.0 < top_p < 1.0:
+            srt, order = logits.sort(-1, descending=True)
+            w = (srt.double() - srt[..., :1].double()).exp()                 # f64: exp(s - max), 0 for filtered entries
+            above = w.cumsum(-1) - w
+            first = torch.ones_like(srt, dtype=torch.bool)
+            first[..., 1:] = srt[..., 1:] != srt[..., :-1]
+            # the mass strictly above: every member of a group of equal values takes its first member's (`above` rises)
+            above = torch.where(first, above, above.new_zeros(())).cummax(-1).values
+            p32 = float(torch.tensor(top_p, dtype=torch.float32))            # the float the device sampler is handed
+            stay = torch.zeros_like(first).scatter(-1, order, above < p32 * w.sum(-1, keepdim=True))
+            logits = logits.masked_fill(~stay, float("-inf"))
         return torch.multinomial(torch.softmax(logits, -1), 1, generator=gen)
 
     # seed-driven decoding: every token drawn on the device (ops.sample_tokens); `done` is read back this often
@@ -144,7 +157,7 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
 
     def _seeded_decode(self, input_ids, vision_masks, attention_mask, max_length, max_new_tokens, head, *, seed, graph,
                        temperature, top_k, cfg=None, force_period=0, force_token=0, eos=None, pad=0, return_logits=False,
-                       kv_dtype=None, prefill_chunk=None):
+                       kv_dtype=None, prefill_chunk=None, top_p=0.0):
         """Decoding with every token chosen by ops.sample_tokens (csrc/sample.h) from the Philox stream of `seed`: the
         sampler also writes the next step's input ids, the output column and the done flags, so no step waits for the
         host.  graph=True: the one-token step -- layers, head, sampler, cache index -- is captured ONCE in a hipGraph
@@ -168,7 +181,7 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
         done = None if eos is None else torch.zeros(B, dtype=torch.uint8, device=dev)
         kw = dict(temperature=float(temperature), top_k=int(top_k or 0), seed=int(seed), cfg_scale=cfg,
                   force_period=force_period, force_token=force_token, done=done, eos=eos, pad=int(pad), tokens_out=tok,
-                  copies=rows // B, seq_out=seq)
+                  copies=rows // B, seq_out=seq, top_p=top_p or None)           # (0.0 = off, as ops._check_top_p returns it)
         logits_out = []
         keep = (lambda lg: logits_out.append(lg.clone())) if return_logits else (lambda lg: None)
         every = self.DONE_CHECK_EVERY
@@ -214,7 +227,7 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
     @torch.no_grad()
     def generate(self, input_ids, vision_masks=None, attention_mask=None, max_new_tokens=16, max_length=None,
                  temperature=1.0, top_k=None, do_sample=False, eos_token_id=None, pad_token_id=0, generator=None,
-                 seed=None, graph=False, return_logits=False, kv_dtype=None, prefill_chunk=None):
+                 seed=None, graph=False, return_logits=False, kv_dtype=None, prefill_chunk=None, top_p=None):
         """Text continuation of a (left-padded) vision-language prompt -- what lwm/vision_chat.py:205-227
         runs with sample_mode='text': prefill over both embedding tables, then one token at a time
         through the text head.  Returns the NEW tokens (B, max_new_tokens), pad after eos (and the f32 logits of
@@ -224,9 +237,13 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
         token drawn on the device by ops.sample_tokens from the Philox stream of `seed` (bf16 or float32 models);
         seed= with graph=True = the same one-token step captured once in a hipGraph and replayed (bf16, one rank).
         With a seed the loop reads `done` back every DONE_CHECK_EVERY tokens instead of after every token.
+        top_p=p, 0 < p < 1: nucleus sampling after temperature and top-k, on every one of these routes by the one rule of
+        include/lwm_hip.h (an entry stays iff the softmax mass strictly above it is below p); None or 1.0 = off, anything
+        else a ValueError; greedy decoding ignores it.
         kv_dtype="fp8": the 8-bit KV cache (LLaMAModel.init_cache), on every one of these routes.  kv_dtype="fp4": the 4-bit
         MXFP4 cache, likewise (no prefill_chunk with it: a block kernel over the 4-bit cache is not built).  prefill_chunk=N: the
         prompt in blocks of N tokens (LLaMAForCausalLM.generate), on every one of these routes too."""
+        top_p = _ops._check_top_p(top_p, "generate")
         if self.cfg.sample_mode != "text":
             raise ValueError("generate() decodes text: set sample_mode='text' (scripts/run_vision_chat.sh)")
         if seed is not None or graph:
@@ -235,7 +252,7 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
                                               self.lm_head, seed=seed, graph=graph,
                                               temperature=temperature if do_sample else 0.0, top_k=top_k,
                                               eos=eos_token_id, pad=pad_token_id, return_logits=return_logits,
-                                              kv_dtype=kv_dtype, prefill_chunk=prefill_chunk)
+                                              kv_dtype=kv_dtype, prefill_chunk=prefill_chunk, top_p=top_p)
             out = out.to(input_ids.dtype)
             return (out, logits) if return_logits else out
         B, S = input_ids.shape
@@ -249,7 +266,7 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
             logits = _head_logits(self, h, head)
             if return_logits:
                 logits_out.append(logits.clone())
-            tok = self._pick(logits, temperature, top_k, do_sample, generator).to(input_ids.dtype)
+            tok = self._pick(logits, temperature, top_k, do_sample, generator, top_p).to(input_ids.dtype)
             out[:, i] = torch.where(done, out[:, i], tok[:, 0])
             if eos_token_id is not None:
                 done |= tok[:, 0] == eos_token_id
@@ -262,7 +279,7 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
     @torch.no_grad()
     def generate_vision(self, input_ids, cfg_scales, attention_mask=None, vision_masks=None, max_new_tokens=257,
                         temperature=1.0, top_k=None, generator=None, max_length=None, seed=None, graph=False,
-                        return_logits=False, kv_dtype=None, prefill_chunk=None):
+                        return_logits=False, kv_dtype=None, prefill_chunk=None, top_p=None):
         """FlaxVideoLLaMAForCausalLM.generate_vision / _sample_vision (lwm/vision_llama.py:476-745):
         the batch holds the conditional prompts followed by the same number of unconditional ones;
         logits = uncond + cfg * (cond - uncond) over the VISION head (sample_mode='vision'), top-k /
@@ -273,7 +290,8 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
         Sampling as generate(): generator= = the torch sampler, eager; seed= = ops.sample_tokens on the device, which
         also mixes the halves, forces the end-of-frame code and feeds both halves; seed= with graph=True = that step
         captured once in a hipGraph and replayed (bf16, one rank).  kv_dtype="fp8" / "fp4": the 8-bit / 4-bit KV cache;
-        prefill_chunk=N: the prompt in blocks of N tokens (LLaMAForCausalLM.generate)."""
+        prefill_chunk=N: the prompt in blocks of N tokens (LLaMAForCausalLM.generate).  top_p as generate()."""
+        top_p = _ops._check_top_p(top_p, "generate_vision")
         if self.cfg.sample_mode != "vision":
             raise ValueError("generate_vision() needs sample_mode='vision' (scripts/run_sample_image.sh)")
         B2, S = input_ids.shape
@@ -287,7 +305,7 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
                                               self._vision_kernel().contiguous(), seed=seed, graph=graph,
                                               temperature=temperature, top_k=top_k, cfg=cfg.reshape(B).contiguous(),
                                               force_period=257, force_token=8192, return_logits=return_logits,
-                                              kv_dtype=kv_dtype, prefill_chunk=prefill_chunk)
+                                              kv_dtype=kv_dtype, prefill_chunk=prefill_chunk, top_p=top_p)
             out = out.to(input_ids.dtype)
             return (out, logits) if return_logits else out
         max_length = max_length or (S + max_new_tokens)
@@ -300,7 +318,7 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
             if return_logits:
                 logits_out.append(logits.clone())
             cond, uncond = logits[:B], logits[B:]
-            tok = self._pick(uncond + cfg * (cond - uncond), temperature, top_k, True, generator).to(input_ids.dtype)
+            tok = self._pick(uncond + cfg * (cond - uncond), temperature, top_k, True, generator, top_p).to(input_ids.dtype)
             if (i + 1) % 257 == 0:
                 tok = torch.full_like(tok, 8192)
             out[:, i] = tok[:, 0]
