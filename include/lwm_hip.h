@@ -846,12 +846,51 @@ int lwm_vq_argmin_f32(const float* z, const float* codebook, const float* se, in
 int lwm_vq_gather_f32(const float* codebook, const int32_t* idx, const float* z, float* out,
                       int64_t N, int32_t E, int32_t D, void* stream);
 
+/* ------------------------------------------------------------------ frame preprocessor (lwm_version() >= 600)
+ * uint8 RGB frames [T,H,W,3] -> f32 [T,size,size,3] in [-1,1]: the resize (Pillow's antialiased bicubic), centre crop
+ * and scale of lwm/vision_chat.py:59-74, bit for bit.  Pillow's 8-bit resample is integer arithmetic on fixed-point
+ * coefficients; the device does that arithmetic and nothing else, and the CALLER supplies the tables (HOST memory;
+ * lwm_amd/frames.py::resample_tables builds them in f64):
+ *
+ *   a pass (`in` samples -> the `size` samples of the crop window) is, per output sample i,
+ *     bounds[i] = {first, taps}                         0 <= first, 1 <= taps <= ksize, first + taps <= in
+ *     coeffs[i][0..taps)                                int32, round(weight * 2^22)
+ *     result = clamp((2^21 + sum_x pixel[first + x] * coeffs[i][x]) >> 22, 0, 255)     (arithmetic shift; the sum
+ *     is taken modulo 2^32: exact while 255 * sum |coeff| + 2^21 < 2^31, which Pillow's tables keep with room to
+ *     spare -- tests/test_frames_ref.py)
+ *   the horizontal pass (h_*: in = W) runs first and its result is rounded to uint8, as Pillow's intermediate image
+ *   is; then the vertical pass (v_*: in = H).  Only the columns and rows of the crop window are tabulated and computed,
+ *   and only the rows that the vertical tables read go through the horizontal pass.
+ *   ksize 0 (bounds and coeffs NULL) = Pillow skips that pass (output length == input length): the window is COPIED,
+ *   from column `left` / row `top` on (otherwise `left` / `top` are ignored).
+ *   scale[256] = the f32 value of each byte, float32(u) / float32(127.5) - float32(1).
+ *
+ * The tables are validated on the host before anything is launched, then copied to the head of `workspace` on
+ * `stream`; they must stay valid until the stream has passed this call.  frames, out, workspace are DEVICE memory;
+ * workspace: 16-byte aligned, lwm_frames_preprocess_workspace_bytes() bytes (tables + the uint8 intermediate image).
+ * LWM_EINVAL: a null pointer, T / H / W / size < 1, a bound pair outside the input, taps > ksize, a window of a
+ * skipped pass outside the input, a workspace that is too small or misaligned. */
+typedef struct LwmFramesArgs {
+    const uint8_t* frames;     /* device [T,H,W,3] */
+    float* out;                /* device [T,size,size,3] */
+    void* workspace;           /* device */
+    int64_t workspace_bytes;
+    const int32_t* h_bounds;   /* host [size,2] */
+    const int32_t* h_coeffs;   /* host [size,h_ksize] */
+    const int32_t* v_bounds;   /* host [size,2] */
+    const int32_t* v_coeffs;   /* host [size,v_ksize] */
+    const float* scale;        /* host [256] */
+    int32_t T, H, W, size, h_ksize, v_ksize, left, top;
+} LwmFramesArgs;
+int64_t lwm_frames_preprocess_workspace_bytes(int32_t T, int32_t H, int32_t size, int32_t h_ksize, int32_t v_ksize);
+int lwm_frames_preprocess_u8(const LwmFramesArgs* args, void* stream);
+
 const char* lwm_last_error(void);
 int lwm_version(void);
 /* sizeof(LwmAttnArgs) (which = 0) / sizeof(LwmConvArgs) (1) / sizeof(LwmRingArgs) (2) / sizeof(LwmGemvArgs) (3) /
  * sizeof(LwmSampleArgs) (4) / sizeof(LwmKv8DecodeArgs) (5) / sizeof(LwmKv8PrefillArgs) (6) / sizeof(LwmAdamWArgs) (7) as
  * sizeof(LwmAdamWTensor) (8: an element of a device table that the caller lays out) / sizeof(LwmGemvW8Args) (9) /
- * sizeof(LwmKv4DecodeArgs) (10) / sizeof(LwmGemvW4Args) (11) as
+ * sizeof(LwmKv4DecodeArgs) (10) / sizeof(LwmGemvW4Args) (11) / sizeof(LwmFramesArgs) (12) as
  * compiled into the library:
  * lets a foreign-language binding verify its struct mirror at load time. */
 int lwm_sizeof(int which);

@@ -185,6 +185,14 @@ class LwmConvArgs(C.Structure):
                     "Wo", "clip")]
 
 
+class LwmFramesArgs(C.Structure):
+    """the tables (h_* / v_* / scale) are HOST pointers; frames, out, workspace are device pointers"""
+    _fields_ = [("frames", C.c_void_p), ("out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+                ("h_bounds", C.c_void_p), ("h_coeffs", C.c_void_p), ("v_bounds", C.c_void_p), ("v_coeffs", C.c_void_p),
+                ("scale", C.c_void_p)] + [(n, C.c_int32) for n in (
+                    "T", "H", "W", "size", "h_ksize", "v_ksize", "left", "top")]
+
+
 # name -> (restype, argtypes); every symbol include/lwm_hip.h declares
 PROTOTYPES = {
     "lwm_attn_fwd": (C.c_int, [C.POINTER(LwmAttnArgs), C.c_void_p]),
@@ -287,6 +295,8 @@ PROTOTYPES = {
     "lwm_vq_sqnorm_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "lwm_vq_argmin_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
     "lwm_vq_gather_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    "lwm_frames_preprocess_workspace_bytes": (C.c_int64, [C.c_int32] * 5),
+    "lwm_frames_preprocess_u8": (C.c_int, [C.POINTER(LwmFramesArgs), C.c_void_p]),
     "lwm_last_error": (C.c_char_p, []),
     "lwm_version": (C.c_int, []),
     "lwm_sizeof": (C.c_int, [C.c_int]),
@@ -302,7 +312,7 @@ def bind(lib):
         fn.argtypes = args
     for which, cls in ((0, LwmAttnArgs), (1, LwmConvArgs), (2, LwmRingArgs), (4, LwmSampleArgs), (5, LwmKv8DecodeArgs),
                        (6, LwmKv8PrefillArgs), (7, LwmAdamWArgs), (8, LwmAdamWTensor), (9, LwmGemvW8Args),
-                       (10, LwmKv4DecodeArgs), (11, LwmGemvW4Args)):
+                       (10, LwmKv4DecodeArgs), (11, LwmGemvW4Args), (12, LwmFramesArgs)):
         if lib.lwm_sizeof(which) != C.sizeof(cls):
             raise ImportError(f"{cls.__name__}: ctypes mirror is {C.sizeof(cls)} bytes, library has "
                               f"{lib.lwm_sizeof(which)} (include/lwm_hip.h and lwm_amd/_capi.py out of step)")

@@ -4,6 +4,7 @@ lwm/vision_chat.py:110-145 -> sampled continuation through the cached-decode hot
 from __future__ import annotations
 
 import math
+import os
 import sys
 
 import numpy as np
@@ -31,14 +32,30 @@ def _process_frame(image, size):
     return np.array(image, dtype=np.float32) / 127.5 - 1
 
 
-def read_frames(path, max_n_frames):
+def frames_route():
+    """LWM_FRAMES: `pil` (the default) = _process_frame, Pillow on one host thread; `hip` = lwm_amd.frames.process_frames,
+    the same arithmetic bit for bit in HIP kernels on the device."""
+    route = os.environ.get("LWM_FRAMES", "pil")
+    if route not in ("hip", "pil"):
+        raise SystemExit(f"LWM_FRAMES={route!r}: expected 'hip' or 'pil'")
+    return route
+
+
+def read_frames(path, max_n_frames, route="pil"):
     """-> (T,256,256,3) f32 in [-1,1].  .png/.jpg (PIL); .npy of (T,H,W,3) uint8 frames (the container has
-    no decord: convert a video with any tool to an array of frames); 'synthetic:<T>' = seeded noise."""
+    no decord: convert a video with any tool to an array of frames); 'synthetic:<T>' = seeded noise.
+    route="hip": decoding, frame selection and the cast to uint8 stay on the host, the resize, crop and scale run on the
+    current device and the result is a device tensor."""
     from PIL import Image
+    if route not in ("hip", "pil"):
+        raise ValueError(f"read_frames: route must be 'hip' or 'pil', got {route!r}")
     if path.startswith("synthetic:"):
         T = int(path.split(":", 1)[1])
         return np.random.default_rng(0).uniform(-1, 1, (min(T, max_n_frames), 256, 256, 3)).astype(np.float32)
     if path.endswith((".png", ".jpg", ".jpeg")):
+        if route == "hip":
+            from ..frames import process_frames
+            return process_frames(np.array(Image.open(path).convert("RGB"), dtype=np.uint8), 256)
         return _process_frame(Image.open(path).convert("RGB"), 256)[None]
     if path.endswith(".npy"):
         video = np.load(path)
@@ -46,6 +63,9 @@ def read_frames(path, max_n_frames):
             raise SystemExit(f"{path}: expected (T,H,W,3) frames")
         ids = list(range(len(video))) if len(video) <= max_n_frames else \
             np.linspace(0, len(video) - 1, max_n_frames, dtype=int).tolist()          # lwm/vision_chat.py:85-88
+        if route == "hip":
+            from ..frames import process_frames
+            return process_frames(video[ids].astype(np.uint8), 256)
         return np.stack([_process_frame(Image.fromarray(video[i].astype(np.uint8)), 256) for i in ids])
     raise SystemExit(f"{path}: unsupported input (png / jpg / npy frames; video containers need decord, which "
                      f"this image does not have)")
@@ -77,8 +97,10 @@ class Sampler:
 
     def _read_process_vision(self, path, max_n_frames):
         """frames -> [256 codes, 8192] per frame, 8193 after the last (lwm/vision_chat.py:76-108)."""
-        vision = read_frames(path, max_n_frames)
-        _, idx = self.vqgan.encode(torch.from_numpy(vision))             # all frames in one call (independent)
+        vision = read_frames(path, max_n_frames, route=frames_route())
+        if isinstance(vision, np.ndarray):
+            vision = torch.from_numpy(vision)
+        _, idx = self.vqgan.encode(vision)                               # all frames in one call (independent)
         enc = idx.reshape(len(vision), -1).cpu().numpy().astype(int)
         out = []
         for t in range(len(enc)):

@@ -19,6 +19,13 @@ inline int zero_device(void* p, size_t bytes, void* stream) {
     return 0;
 }
 
+// host -> device copy on the stream (small tables: the source may be pageable memory)
+inline int copy_to_device(void* dst, const void* src, size_t bytes, void* stream) {
+    hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(-3, "%s: hipMemcpyAsync: %ld", "copy_to_device", (long)e);
+    return 0;
+}
+
 // compute units of the current device (persistent kernels launch one workgroup per CU)
 inline long device_cu_count() {
     static thread_local int cached_dev = -1;

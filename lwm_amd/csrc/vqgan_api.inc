@@ -2,9 +2,52 @@
 // validation, tile-shape selection, launches.  Included by lwm_vqgan.hip (product)
 // and tests/emu/lwm_emu.cpp (host emulation, test-only).
 
+#include "frames.h"
+
 namespace lwm {
 
 static bool vq_aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+
+#ifdef LWM_EMU      // (the product's is in launch.h)
+static int copy_to_device(void* dst, const void* src, size_t bytes, void* stream) {
+    (void)stream;
+    memcpy(dst, src, bytes);
+    return 0;
+}
+#endif
+
+// workspace of the frame preprocessor: [h bounds | h coeffs | v bounds | v coeffs | scale] as 4-byte words, rounded up
+// to 16 bytes, then the uint8 intermediate image
+static int64_t frames_table_bytes(int64_t size, int64_t hks, int64_t vks) {
+    const int64_t words = (hks ? size * (2 + hks) : 0) + (vks ? size * (2 + vks) : 0) + 256;
+    return (words * 4 + 15) & ~(int64_t)15;
+}
+static int64_t frames_istride(int64_t size) { return (size * 3 + 3) & ~(int64_t)3; }
+
+// one pass's tables against its input length; *lo / *hi: the input samples [lo, hi) that the pass reads
+static int frames_check_pass(const char* which, const int32_t* bounds, const int32_t* coeffs, int32_t ksize, int32_t size,
+                             int32_t n_in, int32_t skip_first, int32_t* lo, int32_t* hi) {
+    if (ksize < 0) return fail(LWM_EINVAL, "frames: %s pass: negative ksize", which);
+    if (ksize == 0) {
+        if (bounds || coeffs) return fail(LWM_EINVAL, "frames: %s pass: ksize 0 with tables", which);
+        if (skip_first < 0 || (int64_t)skip_first + size > n_in)
+            return fail(LWM_EINVAL, "frames: %s pass skipped: window at %ld leaves the input of %ld", which, skip_first, n_in);
+        *lo = skip_first;
+        *hi = skip_first + size;
+        return LWM_OK;
+    }
+    if (!bounds || !coeffs) return fail(LWM_EINVAL, "frames: %s pass: null table", which);
+    *lo = n_in;
+    *hi = 0;
+    for (int32_t i = 0; i < size; ++i) {
+        const int64_t first = bounds[2 * i], taps = bounds[2 * i + 1];
+        if (first < 0 || taps < 1 || taps > ksize || first + taps > n_in)
+            return fail(LWM_EINVAL, "frames: %s pass: bounds of output %ld leave the input or exceed ksize", which, i);
+        if (first < *lo) *lo = (int32_t)first;
+        if (first + taps > *hi) *hi = (int32_t)(first + taps);
+    }
+    return LWM_OK;
+}
 
 // number of statistics slices for a GroupNorm over HW pixels
 static int gn_slices(int64_t HW) {
@@ -151,6 +194,78 @@ int lwm_vq_gather_f32(const float* codebook, const int32_t* idx, const float* z,
     long blocks = (long)((N * (D / 4) + 255) / 256);
     if (blocks > 8192) blocks = 8192;
     return launch("vq_gather", vq_gather_kernel, blocks, 256, 0, stream, codebook, idx, z, out, N, (int)D, (int)E);
+}
+
+int64_t lwm_frames_preprocess_workspace_bytes(int32_t T, int32_t H, int32_t size, int32_t h_ksize, int32_t v_ksize) {
+    if (T < 1 || H < 1 || size < 1 || h_ksize < 0 || v_ksize < 0) return 0;
+    // (the intermediate image holds at most all H rows of the `size` cropped columns)
+    return lwm::frames_table_bytes(size, h_ksize, v_ksize) + (int64_t)T * H * lwm::frames_istride(size);
+}
+
+int lwm_frames_preprocess_u8(const LwmFramesArgs* a, void* stream) {
+    using namespace lwm;
+    if (!a) return fail(LWM_EINVAL, "%s", "frames: args is null");
+    if (!a->frames || !a->out || !a->workspace || !a->scale) return fail(LWM_EINVAL, "%s", "frames: null pointer");
+    if (a->T < 1 || a->H < 1 || a->W < 1 || a->size < 1) return fail(LWM_EINVAL, "%s", "frames: T, H, W, size must be >= 1");
+    if ((int64_t)a->H * a->W * 3 >= (1LL << 31) || a->size > 16384)
+        return fail(LWM_EUNSUPPORTED, "%s: one frame holds 2^31 bytes or more, or size > 16384 (H x W = %ld x %ld)", "frames", (long)a->H, (long)a->W);
+    // every table entry is checked here, on the host, before anything is launched: the kernels index with them
+    int32_t clo, chi, rlo, rhi;
+    int r;
+    if ((r = frames_check_pass("horizontal", a->h_bounds, a->h_coeffs, a->h_ksize, a->size, a->W, a->left, &clo, &chi))) return r;
+    if ((r = frames_check_pass("vertical", a->v_bounds, a->v_coeffs, a->v_ksize, a->size, a->H, a->top, &rlo, &rhi))) return r;
+    if (!vq_aligned16(a->workspace)) return fail(LWM_EINVAL, "%s", "frames: workspace not 16-byte aligned");
+    if (a->workspace_bytes < lwm_frames_preprocess_workspace_bytes(a->T, a->H, a->size, a->h_ksize, a->v_ksize))
+        return fail(LWM_EINVAL, "frames: workspace of %s%ld bytes, need %ld", "", (long)a->workspace_bytes,
+                    (long)lwm_frames_preprocess_workspace_bytes(a->T, a->H, a->size, a->h_ksize, a->v_ksize));
+
+    FramesParams p;
+    p.frames = a->frames; p.out = a->out;
+    p.T = a->T; p.H = a->H; p.W = a->W; p.size = a->size; p.hks = a->h_ksize; p.vks = a->v_ksize;
+    p.left = a->left; p.top = a->top;
+    p.total = (int64_t)a->T * a->H * a->W * 3;
+    p.row0 = rlo; p.nrows = rhi - rlo;
+    p.istride = (int32_t)frames_istride(a->size);
+    p.nstrips = (a->size + kFrCols - 1) / kFrCols;
+    p.nrblocks = (p.nrows + kFrRowsPerWg - 1) / kFrRowsPerWg;
+    // the widest input span of a strip of output columns sizes the staged rows (+ the misalignment of a row's first
+    // byte, + the dword that frames_px reads past a pixel)
+    int32_t span = 0;
+    for (int32_t s = 0; s < p.nstrips; ++s) {
+        const int32_t x0 = s * kFrCols, x1 = x0 + kFrCols < a->size ? x0 + kFrCols : a->size;
+        int32_t lo = a->W, hi = 0;
+        if (!a->h_ksize) { lo = x0; hi = x1; }
+        for (int32_t i = x0; a->h_ksize && i < x1; ++i) {
+            const int32_t first = a->h_bounds[2 * i], end = first + a->h_bounds[2 * i + 1];
+            lo = first < lo ? first : lo;
+            hi = end > hi ? end : hi;
+        }
+        span = hi - lo > span ? hi - lo : span;
+    }
+    p.span_dw = (span * 3 + 6) / 4 + 2;
+    const size_t lds = frames_hpass_lds(p.hks, p.span_dw);
+    if (lds > 160 * 1024)
+        return fail(LWM_EUNSUPPORTED, "%s: a strip of output columns reads %ld input columns with %ld taps: over the LDS", "frames", (long)span, (long)a->h_ksize);
+    const int64_t hgrid = (int64_t)a->T * p.nrblocks * p.nstrips;
+    const int64_t vgrid = (int64_t)a->T * (((int64_t)a->size * (p.istride / 4) + kFrThreads - 1) / kFrThreads);
+    if (hgrid > 0x7fffffffLL || vgrid > 0x7fffffffLL) return fail(LWM_EINVAL, "%s", "frames: grid too large");
+
+    // tables -> the head of the workspace, in the order of frames_table_bytes
+    int32_t* w = (int32_t*)a->workspace;
+    auto put = [&](const void* src, int64_t words) -> const int32_t* {
+        const int32_t* at = w;
+        if (!r) r = copy_to_device(w, src, (size_t)words * 4, stream);
+        w += words;
+        return at;
+    };
+    p.hb = p.hk = p.vb = p.vk = nullptr;
+    if (a->h_ksize) { p.hb = put(a->h_bounds, (int64_t)a->size * 2); p.hk = put(a->h_coeffs, (int64_t)a->size * a->h_ksize); }
+    if (a->v_ksize) { p.vb = put(a->v_bounds, (int64_t)a->size * 2); p.vk = put(a->v_coeffs, (int64_t)a->size * a->v_ksize); }
+    p.scale = (const float*)put(a->scale, 256);
+    if (r) return r;
+    p.inter = (uint8_t*)a->workspace + frames_table_bytes(a->size, a->h_ksize, a->v_ksize);
+    if ((r = launch("frames_hpass", frames_hpass_kernel, (long)hgrid, kFrThreads, lds, stream, p))) return r;
+    return launch("frames_vpass", frames_vpass_kernel, (long)vgrid, kFrThreads, 0, stream, p);
 }
 
 }  // extern "C"
