@@ -117,6 +117,17 @@ typedef struct LwmAttnArgs {
      * refuse a buffer smaller than lwm_attn_bwd_delta_bytes(B,H,Sq) instead of overrunning it (the layout of the
      * statistics changed at lwm_version() 400: a [B,H,Sq] buffer of earlier versions is too small). */
     int64_t delta_bytes;
+    /* dS hand-over (lwm_version() >= 610), backward only, optional: a workspace of lwm_attn_bwd_ds_bytes(...) bytes,
+     * 16-byte aligned.  lwm_attn_bwd_dkdv then also stores the dS it computes (bf16, in a layout private to the two
+     * kernels), and lwm_attn_bwd_dq called AFTERWARDS on the same stream with the same arguments computes
+     * dq = scale * dS k from it in one GEMM instead of recomputing S and dP: 7 GEMM units per pair instead of 9.
+     * dk and dv are bitwise what they are without it; dq differs in rounding only (its dS comes from the dK/dV kernel's
+     * chains).  Honoured when lwm_attn_bwd_ds_bytes is not 0 for the call and the call has bf16 operands, no
+     * segment ids, no key_valid, final_out = 1, carry_in = 0 and one piece per operand; any other call ignores the
+     * workspace and runs as without it.  A workspace that is too small or misaligned for an eligible call: LWM_EINVAL,
+     * nothing is launched.  NULL = no hand-over. */
+    void* ds_ws;
+    int64_t ds_ws_bytes;
 } LwmAttnArgs;
 
 int lwm_attn_fwd(const LwmAttnArgs* args, void* stream);
@@ -131,6 +142,11 @@ int lwm_attn_bwd_dkdv(const LwmAttnArgs* args, void* stream);
 
 /* Bytes of the backward's row statistics (LwmAttnArgs::delta) for a [B, Sq, H, D] query block. */
 int64_t lwm_attn_bwd_delta_bytes(int32_t B, int32_t H, int32_t Sq);
+/* Exact bytes of the dS hand-over workspace (LwmAttnArgs::ds_ws) of one (query block, K/V block) pair, or 0 when the
+ * shape is not eligible (Sq % 64, Sk % 128) or there is nothing to hand over.  Only the (64 queries x 32 keys) tiles
+ * the dK/dV walk visits get room: causal, a tile wholly above the diagonal has none -- B * H * Sq * Sk bytes for a
+ * causal square pair, twice that without the mask (32 GiB at B = 1, H = 32, Sq = Sk = 32768, causal). */
+int64_t lwm_attn_bwd_ds_bytes(int32_t B, int32_t H, int32_t Sq, int32_t Sk, int32_t causal, int64_t q_start, int64_t k_start);
 
 /* ------------------------------------------------------------------ the float32 flavour of the training op
  * The reference computes in `--dtype`, and its own default is fp32 (lwm/train.py:36; the launch scripts of

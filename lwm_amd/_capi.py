@@ -54,6 +54,7 @@ class LwmAttnArgs(C.Structure):
         ("q_piece_row", C.c_int32 * MAX_PIECES), ("k_piece_row", C.c_int32 * MAX_PIECES),
         ("q_piece_pos", C.c_int64 * MAX_PIECES), ("k_piece_pos", C.c_int64 * MAX_PIECES),
         ("delta_bytes", C.c_int64),
+        ("ds_ws", C.c_void_p), ("ds_ws_bytes", C.c_int64),
     ]
 
 
@@ -200,6 +201,7 @@ PROTOTYPES = {
     "lwm_attn_bwd_dq": (C.c_int, [C.POINTER(LwmAttnArgs), C.c_void_p]),
     "lwm_attn_bwd_dkdv": (C.c_int, [C.POINTER(LwmAttnArgs), C.c_void_p]),
     "lwm_attn_bwd_delta_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "lwm_attn_bwd_ds_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64]),
     "lwm_attn_fwd_f32": (C.c_int, [C.POINTER(LwmAttnArgs), C.c_void_p]),
     "lwm_attn_bwd_delta_f32": (C.c_int, [C.POINTER(LwmAttnArgs), C.c_void_p]),
     "lwm_attn_bwd_dq_f32": (C.c_int, [C.POINTER(LwmAttnArgs), C.c_void_p]),

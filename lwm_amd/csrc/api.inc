@@ -393,6 +393,19 @@ int lwm_attn_bwd_delta(const LwmAttnArgs* a, void* stream) {
     return launch("attn_bwd_delta", attn_bwd_delta_kernel, blocks, kDeltaThreads, 0, stream, p, a->delta);
 }
 
+// dS hand-over (attn_bwd64.h): 1 = this call takes it, 0 = it runs as without a workspace, < 0 = refused
+static int ds_handover(const char* who, const LwmAttnArgs* a) {
+    using namespace lwm;
+    if (!a->ds_ws) return 0;
+    if (a->segment_ids_k || a->key_valid || !a->final_out || a->carry_in || a->q_pieces > 1 || a->k_pieces > 1) return 0;
+    const int64_t need = lwm_attn_bwd_ds_bytes(a->B, a->H, a->Sq, a->Sk, a->causal, a->q_start, a->k_start);
+    if (need == 0) return 0;
+    if (!aligned16(a->ds_ws)) return fail(LWM_EINVAL, "%s: ds_ws is not 16-byte aligned", who);
+    if (a->ds_ws_bytes < need)
+        return fail(LWM_EINVAL, "%s: ds_ws holds %ld bytes, lwm_attn_bwd_ds_bytes asks for %ld", who, (long)a->ds_ws_bytes, (long)need);
+    return 1;
+}
+
 int lwm_attn_bwd_dq(const LwmAttnArgs* a, void* stream) {
     using namespace lwm;
     int r;
@@ -405,6 +418,12 @@ int lwm_attn_bwd_dq(const LwmAttnArgs* a, void* stream) {
     if (a->carry_in && !a->dq_acc) return fail(LWM_EINVAL, "%s", "bwd_dq: carry_in needs dq_acc");
     if (a->B == 0 || a->Sq == 0) return LWM_OK;
     AttnParams p = to_params(a);
+    if ((r = ds_handover("bwd_dq", a)) < 0) return r;
+    if (r) {      // dq = scale * dS k from the dS the dK/dV kernel left in the workspace: 64 queries per wave
+        p.ds_ws = (char*)a->ds_ws;
+        const long nqb = (p.Sq + kS4BQ - 1) / kS4BQ;
+        return launch("attn_bwd_dq_ds", attn_bwd_dq_ds_kernel, nqb * p.H * p.B, kD4Threads, kS4LdsBytes, stream, p);
+    }
     // one wave per SIMD, 32 queries per wave (attn_bwd64.h); the variant with key meta when a key can be masked for
     // another reason than causality (segments, padded keys, a ragged last 64-key step)
     const long nqb = (p.Sq + kQ4BQ - 1) / kQ4BQ;
@@ -430,6 +449,11 @@ int lwm_attn_bwd_dkdv(const LwmAttnArgs* a, void* stream) {
     // one wave per SIMD, 32 keys per wave (attn_bwd64.h); the variant with key meta only when a key can be masked
     // for another reason than causality
     const long nkb = (p.Sk + kD4BK - 1) / kD4BK;
+    if ((r = ds_handover("bwd_dkdv", a)) < 0) return r;
+    if (r) {
+        p.ds_ws = (char*)a->ds_ws;
+        return launch("attn_bwd_dkdv4_ds", attn_bwd_dkdv4_ds_kernel, nkb * p.H * p.B, kD4Threads, kD4LdsBytes, stream, p);
+    }
     if (p.seg_k || p.key_valid)
         return launch("attn_bwd_dkdv4_meta", attn_bwd_dkdv4_meta_kernel, nkb * p.H * p.B, kD4Threads, kD4LdsBytes, stream, p);
     return launch("attn_bwd_dkdv4", attn_bwd_dkdv4_kernel, nkb * p.H * p.B, kD4Threads, kD4LdsBytes, stream, p);
@@ -438,6 +462,12 @@ int lwm_attn_bwd_dkdv(const LwmAttnArgs* a, void* stream) {
 int64_t lwm_attn_bwd_delta_bytes(int32_t B, int32_t H, int32_t Sq) {
     if (B <= 0 || H <= 0 || Sq <= 0) return 0;
     return (int64_t)B * H * 2 * lwm::bwd_stat_pad(Sq) * (int64_t)sizeof(float);
+}
+
+int64_t lwm_attn_bwd_ds_bytes(int32_t B, int32_t H, int32_t Sq, int32_t Sk, int32_t causal, int64_t q_start, int64_t k_start) {
+    using namespace lwm;
+    if (B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0 || (Sq % kD4BQ) || (Sk % kD4BK)) return 0;
+    return ds_ws_bytes(B, H, Sq, Sk, causal ? 1 : 0, q_start, k_start);
 }
 
 int lwm_cast_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream) {
@@ -968,7 +998,7 @@ int lwm_adamw_step(const LwmAdamWArgs* a, void* stream) {
 int lwm_adamw_chunk(void) { return lwm::kAdamWChunk; }
 
 const char* lwm_last_error(void) { return lwm::g_err; }
-int lwm_version(void) { return 600; }
+int lwm_version(void) { return 610; }
 int lwm_sizeof(int which) {
     return which == 0 ? (int)sizeof(LwmAttnArgs) : which == 1 ? (int)sizeof(LwmConvArgs) : which == 2 ? (int)sizeof(LwmRingArgs) : which == 3 ? (int)sizeof(LwmGemvArgs) : which == 4 ? (int)sizeof(LwmSampleArgs) : which == 5 ? (int)sizeof(LwmKv8DecodeArgs) : which == 6 ? (int)sizeof(LwmKv8PrefillArgs) : which == 7 ? (int)sizeof(LwmAdamWArgs) : which == 8 ? (int)sizeof(LwmAdamWTensor) : which == 9 ? (int)sizeof(LwmGemvW8Args) : which == 10 ? (int)sizeof(LwmKv4DecodeArgs) : which == 11 ? (int)sizeof(LwmGemvW4Args) : which == 12 ? (int)sizeof(LwmFramesArgs) : -1;
 }

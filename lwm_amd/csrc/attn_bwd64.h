@@ -171,6 +171,94 @@ LWM_DEVICE void q4_settle_acc(f32x4 (&a)[16]) {
 }
 #endif
 
+// ====================================================================================================== dS hand-over
+// The dK/dV kernel holds every dS it computes as packed bf16 B operands of its dK chain; the recompute dQ kernel spends
+// two of its three GEMM units on producing the same numbers again.  With a workspace (LwmAttnArgs::ds_ws) the dK/dV
+// kernel stores them and attn_bwd_dq_ds_kernel (end of the file) computes dQ = scale * dS K from them in ONE unit.
+//
+// Workspace = tiles of kDsTileBytes: tile (b, h, key block kbi, wave w, step st) = the dS of the 64 queries of step st
+// against the 32 keys of wave w of key block kbi, in the order the dK/dV walk leaves them:
+//   [unit = query half of the step: 2][key half kh: 2][lane (c, g) of the producer: 64][16 bytes]
+// where the lane's 16 bytes are its dK-chain operand as it stands: key 16 kh + c, queries 4g .. 4g+3 | 16+4g .. 16+4g+3
+// of the unit.  Only the steps a key block's walk visits have a tile (causal: steps from ds_first_step on -- the others
+// lie wholly before the block's first key and every dS there is 0), rows of tiles are laid out [b, h][kbi][w][st - first],
+// so that a wave's walk writes one run of memory (descending) and the four waves of a consumer workgroup read 16
+// consecutive KiB per key step.  Eligible calls have one piece per operand, Sq % 64 == 0, Sk % 128 == 0 and no key meta,
+// so everything below is a function of (causal, q_start, k_start, Sq, Sk) -- the same on the host (api.inc sizes the
+// workspace with it) and in both kernels.
+constexpr int kDsTileBytes = kD4BQ * 32 * 2;      // 4 KiB
+// e: step st is visited by key block kbi iff st >= e + 2 kbi (the kernel's tiles_below on one piece: the steps wholly
+// before key k_start + 128 kbi are the first floor((k_start - q_start + 128 kbi) / 64)); not causal: every step
+constexpr int64_t ds_diag(int causal, int64_t q_start, int64_t k_start) {
+    const int64_t lim = (int64_t)1 << 30, e = (k_start - q_start) >> 6;
+    return !causal ? -lim : (e < -lim ? -lim : (e > lim ? lim : e));
+}
+constexpr int64_t ds_first_step(int64_t e, int64_t nst, int64_t kbi) {
+    const int64_t s = e + 2 * kbi;
+    return s < 0 ? 0 : (s > nst ? nst : s);
+}
+// tiles per wave in the key blocks before kbi: sum over j < kbi of nst - ds_first_step(e, nst, j), in closed form
+constexpr int64_t ds_steps_before(int64_t e, int64_t nst, int64_t kbi) {
+    const int64_t jl = e >= 0 ? 0 : (1 - e) >> 1;               // first key block with e + 2 j >= 0
+    const int64_t jh0 = e >= nst ? 0 : (nst - e + 1) >> 1;      // first key block with e + 2 j >= nst
+    const int64_t jh = jh0 > jl ? jh0 : jl;
+    const int64_t a = kbi < jl ? kbi : jl, b = kbi < jh ? kbi : jh;
+    return kbi * nst - ((b - a) * e + (b - a) * (a + b - 1) + (kbi - b) * nst);
+}
+constexpr bool ds_geom_ok() {
+    const int64_t es[] = {-(1 << 30), -1000, -9, -8, -3, -2, -1, 0, 1, 2, 3, 7, 8, 9, 40, 1 << 30};
+    const int64_t ns[] = {1, 2, 3, 4, 6, 8, 9, 32};
+    for (int64_t e : es)
+        for (int64_t nst : ns) {
+            int64_t sum = 0;
+            for (int64_t kbi = 0; kbi < 24; ++kbi) {
+                if (ds_steps_before(e, nst, kbi) != sum) return false;
+                sum += nst - ds_first_step(e, nst, kbi);
+            }
+        }
+    return true;
+}
+static_assert(ds_geom_ok(), "closed form of the workspace row offsets disagrees with the sum it stands for");
+// 32-key steps of the consumer's walk that hold a tile for query step s (they are the FIRST ones: ds_first_step ascends
+// with the key block); 0 for a step past the operand
+constexpr int64_t ds_wave_steps(int64_t e, int64_t nst, int64_t nkb, int64_t s) {
+    if (s >= nst) return 0;
+    const int64_t kend = s - e < 0 ? 0 : ((s - e) >> 1) + 1;
+    return 4 * (kend < nkb ? kend : nkb);
+}
+// bytes of the workspace (0: nothing to hand over)
+constexpr int64_t ds_ws_bytes(int64_t B, int64_t H, int64_t Sq, int64_t Sk, int causal, int64_t q_start, int64_t k_start) {
+    return B * H * ds_steps_before(ds_diag(causal, q_start, k_start), Sq / kD4BQ, Sk / kD4BK) * 4 * kDsTileBytes;
+}
+
+// The producer's side: unit u's dS leave from the gaps W of the schedule table (phase X of unit u+1, or the drain), one
+// lane-linear 16-byte store per key half = 1 KiB per instruction.  sw.p = the tile of the RUNNING step + kDsTileBytes, a
+// scalar pointer that steps down with the walk, so that both cases fit the instruction's 13-bit offset: the first unit
+// of the running step (stored from the step's second X phase) at BASE = -kDsTileBytes, the second unit of the step
+// BEFORE (stored from the running step's first X phase, or from the drain) at BASE = kDsTileBytes / 2.
+struct D4Ds {
+    char* p;
+    uint32_t v;         // 16 * lane
+};
+#ifdef LWM_EMU
+LWM_DEVICE char* ds_uniform_ptr(char* p) { return p; }
+template <int OFF>
+LWM_DEVICE void d4_ds_store(const D4Ds& sw, bf16x8 x) { memcpy(sw.p + OFF + sw.v, &x, 16); }
+#else
+LWM_DEVICE char* ds_uniform_ptr(char* p) {
+    const uint64_t a = (uint64_t)p;
+    return (char*)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(a >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)a));
+}
+// (asm: hipcc does not count it, so it neither waits for it nor drains the LDS-DMA pieces around it.  Non-temporal: the
+// tiles are read once, by another kernel, and 34 GB of them per layer at the bench shape would push the Q / dO tiles the
+// key blocks of an XCD share out of its L2 -- measured: 17.2 ms with the hint, 18.4 ms without, 13.4 ms with no stores)
+template <int OFF>
+LWM_DEVICE void d4_ds_store(const D4Ds& sw, bf16x8 x) {
+    static_assert(OFF >= -4096 && OFF <= 4095, "13-bit signed instruction offset");
+    asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3 nt" ::"v"(sw.v), "v"(x), "s"(sw.p), "n"(OFF) : "memory");
+}
+#endif
+
 // ====================================================================================================== dK/dV
 struct D4Ctx {
     uint32_t qa[4];             // Q row-fragment addresses (d step s of 32), rows 0..15 of the CURRENT step's Q tile
@@ -274,8 +362,11 @@ LWM_DEVICE bf16x8 d4_frag(const D4Ctx& cx, int f) {
 //   P(i)  P words -> bf16         behind E(2i), E(2i+1); the products of Y(u) read the OLD words to their last MFMA:
 //   D(i)  dS words -> bf16        G >= 32; D(i) behind M(2i), M(2i+1); everything done by G = 61
 // The words of a key half are four consecutive packed registers, ready as the B operand of Y.
+//   W(h)  dS of key half h -> HBM   (hand-over instantiation only, "dS hand-over" below) behind the half's last D; in
+//                                 gap 63: behind the last LDS-DMA piece of a step's first phase, so that the stores are
+//                                 the YOUNGEST vector-memory operations of a step and its counted wait leaves them in flight
 struct D4Sched {
-    int F[16], E[16], M[16], P[8], D[8];
+    int F[16], E[16], M[16], P[8], D[8], W[2];
 };
 constexpr bool d4_sched_ok(const D4Sched& c) {
     int load[64] = {};
@@ -291,6 +382,11 @@ constexpr bool d4_sched_ok(const D4Sched& c) {
         load[c.P[i]] += 1;
         load[c.D[i]] += 1;
     }
+    for (int h = 0; h < 2; ++h) {
+        if (c.W[h] != 63) return false;
+        for (int i = 4 * h; i < 4 * h + 4; ++i)
+            if (c.W[h] <= c.D[i]) return false;
+    }
     for (int g = 0; g < 64; ++g)
         if (load[g] > 2) return false;      // (in units of a plain VALU's issue; an exp counts two)
     return true;
@@ -301,7 +397,8 @@ constexpr D4Sched kD4Sched = {
     /* E */ {11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26},
     /* M */ {27, 27, 28, 28, 29, 29, 30, 30, 31, 31, 32, 32, 33, 33, 34, 34},
     /* P */ {35, 35, 36, 36, 37, 37, 38, 38},
-    /* D */ {39, 39, 40, 40, 41, 41, 42, 42}};
+    /* D */ {39, 39, 40, 40, 41, 41, 42, 42},
+    /* W */ {63, 63}};
 static_assert(d4_sched_ok(kD4Sched), "filler schedule violates a dependency or the issue budget of a gap");
 
 // the LDS-DMA pieces one step issues (all wave-uniform but the offsets): Q and dO of the step two ahead
@@ -351,6 +448,13 @@ LWM_DEVICE void d4_fillers(const D4Ctx& cx, D4Regs& rg) {
     }
 }
 
+// the hand-over stores scheduled in gap G (the unit's tile half begins at sw.p + BASE)
+template <int G, int BASE>
+LWM_DEVICE void d4_ds_stores(const D4Ds& sw, const D4Regs& rg) {
+    if constexpr (kD4Sched.W[0] == G) d4_ds_store<BASE>(sw, rg.dsb[0]);
+    if constexpr (kD4Sched.W[1] == G) d4_ds_store<BASE + 1024>(sw, rg.dsb[1]);
+}
+
 // Every MFMA index below is a template parameter (the phases are recursions, not loops): fragment, tile and filler
 // selection must be constants, or the register arrays they index go to scratch.
 //
@@ -358,9 +462,9 @@ LWM_DEVICE void d4_fillers(const D4Ctx& cx, D4Regs& rg) {
 // fragment consumed first: one wait per four MFMAs), key half ((M>>1)^M)&1; fillers: gaps 32..63 of unit u-1.  A dependent
 // MFMA finds its predecessor eight MFMAs back.  The first kD4Ahead fragments are ALREADY in the ring, rg.ndl holds the
 // unit's -delta; the unit's -lse * log2 e is read here (needed from gap 3 of phase Y).
-template <int HALF, bool HAS_PREV, bool DMA, int M = 0>
+template <int HALF, bool HAS_PREV, bool DMA, bool DS, int M = 0>
 LWM_DEVICE void d4_x(const D4Ctx& cx, D4Regs& rg, const bf16x8 (&kf)[8], const bf16x8 (&vf)[8], const uint32_t (&vq)[4],
-                     const uint32_t (&vdo)[4], const D4Dma& dm) {
+                     const uint32_t (&vdo)[4], const D4Dma& dm, const D4Ds& sw) {
     if constexpr (M < 32) {
         if constexpr ((M & 3) == 0) {
             constexpr int f0 = (M >> 1) + kD4Ahead;
@@ -391,8 +495,9 @@ LWM_DEVICE void d4_x(const D4Ctx& cx, D4Regs& rg, const bf16x8 (&kf)[8], const b
             else f4_dma1(vdo[j], dm.do_src, dm.dst + kD4TileBytes + 4096 * j);
         }
         if constexpr (HAS_PREV) d4_fillers<32 + M, HALF ^ 1>(cx, rg);
+        if constexpr (HAS_PREV && DS) d4_ds_stores<32 + M, HALF == 1 ? -kDsTileBytes : kDsTileBytes / 2>(sw, rg);
         sched_fence();
-        d4_x<HALF, HAS_PREV, DMA, M + 1>(cx, rg, kf, vf, vq, vdo, dm);
+        d4_x<HALF, HAS_PREV, DMA, DS, M + 1>(cx, rg, kf, vf, vq, vdo, dm, sw);
     }
 }
 
@@ -452,11 +557,12 @@ LWM_DEVICE void d4_y(const D4Ctx& cx, D4Regs& rg, f32x4 (&dk)[16], f32x4 (&dv)[1
 
 // the pipeline's tail: the second half of the last unit's vector work, then its dV / dK products (no fillers left).
 // PAR = the parity of the last unit (its dP' tiles); its tiles are addressed as the "previous unit" of a HALF = 0 unit.
-template <int PAR, int G = 32>
-LWM_DEVICE void d4_drain_fill(const D4Ctx& cx, D4Regs& rg) {
+template <int PAR, bool DS, int G = 32>
+LWM_DEVICE void d4_drain_fill(const D4Ctx& cx, D4Regs& rg, const D4Ds& sw) {
     if constexpr (G < 64) {
         d4_fillers<G, PAR>(cx, rg);
-        d4_drain_fill<PAR, G + 1>(cx, rg);
+        if constexpr (DS) d4_ds_stores<G, kDsTileBytes / 2>(sw, rg);      // (the pointer has moved on: as a step's first phase)
+        d4_drain_fill<PAR, DS, G + 1>(cx, rg, sw);
     }
 }
 template <int H, int J = 0>
@@ -469,9 +575,9 @@ LWM_DEVICE void d4_drain_mfma(D4Regs& rg, f32x4 (&dk)[16], f32x4 (&dv)[16]) {
         d4_drain_mfma<H, J + 1>(rg, dk, dv);
     }
 }
-template <int PAR>
-LWM_DEVICE void d4_drain(const D4Ctx& cx, D4Regs& rg, f32x4 (&dk)[16], f32x4 (&dv)[16]) {
-    d4_drain_fill<PAR>(cx, rg);
+template <int PAR, bool DS>
+LWM_DEVICE void d4_drain(const D4Ctx& cx, D4Regs& rg, f32x4 (&dk)[16], f32x4 (&dv)[16], const D4Ds& sw) {
+    d4_drain_fill<PAR, DS>(cx, rg, sw);
 #pragma unroll
     for (int j = 0; j < 8; ++j) rg.fr[j] = d4_frag<0>(cx, 16 + j);
     sched_fence();
@@ -549,8 +655,9 @@ LWM_DEVICE void d4_store_tiles(const AttnParams& p, lds_t tb, const f32x4 (&dk)[
     }
 }
 
-template <bool HAS_META>
+template <bool HAS_META, bool DS = false>
 LWM_DEVICE void attn_bwd_dkdv4_body(const AttnParams& p) {
+    static_assert(!(HAS_META && DS), "the hand-over has no key meta");
 #ifdef LWM_PROF
     // (dump slots 11..13: entry -> last store issued, entry -> first step of the walk, entry -> first store of the epilogue)
     const unsigned long long d4_entry = __builtin_amdgcn_s_memtime();
@@ -753,6 +860,14 @@ LWM_DEVICE void attn_bwd_dkdv4_body(const AttnParams& p) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) rg.fr[j] = zero_bf16x8();
         D4Dma dm = {};
+        // hand-over: the tile of the walk's first step (the LAST step of the wave's row), see d4_ds_stores
+        D4Ds sw = {};
+        if (DS) {
+            const int64_t e = ds_diag(p.causal, p.q_start, p.k_start);
+            const int64_t tile = ((int64_t)hb * ds_steps_before(e, nst, nkb) + ds_steps_before(e, nst, kbi)) * 4 + (int64_t)wave * n + (n - 1);
+            sw.p = ds_uniform_ptr(p.ds_ws + (tile + 1) * kDsTileBytes);
+            sw.v = (uint32_t)lane * 16;
+        }
         // the first unit's fragments and -delta (every later unit finds them requested by the unit before it)
 #pragma unroll
         for (int j = 0; j < kD4Ahead; ++j) rg.fr[j] = d4_frag<0>(cx, j);
@@ -820,14 +935,14 @@ LWM_DEVICE void attn_bwd_dkdv4_body(const AttnParams& p) {
         const uint32_t d_ = (((i) & 3) == 3) ? (uint32_t)(-3 * kD4SlotBytes) : (uint32_t)kD4SlotBytes;             \
         const uint32_t e_ = (((i) & 3) == 3) ? (uint32_t)(-3 * kD4StatBytes) : (uint32_t)kD4StatBytes;             \
         const int32_t segw_ = HAS_META ? seg_step_word(cx.stat - 16 * g4 + 2 * kD4BQ * 4, lane) : 0;                \
-        d4_x<0, !(FIRST), PIPE>(cx, rg, kf, vf, vq, vdo, dm);                                                       \
+        d4_x<0, !(FIRST), PIPE, DS>(cx, rg, kf, vf, vq, vdo, dm, sw);                                                       \
         const bool uni_ = HAS_META && seg_step_uniform(segw_, own_uniform, own_seg);                                \
         D4_LAP2(0);                                                                                                 \
         LWM_D4_MASK(0, !(FIRST), ub);                                                                               \
         D4_LAP2(1);                                                                                                 \
         d4_y<0, !(FIRST), true, false>(cx, rg, dk, dv, cx.stat);                                                    \
         D4_LAP2(2);                                                                                                 \
-        d4_x<1, true, false>(cx, rg, kf, vf, vq, vdo, dm);                                                          \
+        d4_x<1, true, false, DS>(cx, rg, kf, vf, vq, vdo, dm, sw);                                                  \
         for (int s_ = 0; s_ < 4; ++s_) cx.qa[s_] += d_;                                                             \
         D4_LAP2(3);                                                                                                 \
         LWM_D4_MASK(1, true, ub + 32);                                                                              \
@@ -838,7 +953,16 @@ LWM_DEVICE void attn_bwd_dkdv4_body(const AttnParams& p) {
         /* wherever control flow merges behind a step (loop entry, loop exit, the short-walk branch) hipcc may */  \
         /* reconcile the accumulator tuples of the two paths by copies: they must find the last MFMAs retired  */  \
         if ((FIRST) || !(PIPE)) d4_settle_acc(dk, dv);                                                              \
-        glds_wait_all();                                                                                            \
+        /* hand-over: the step's four dS stores are its youngest vector-memory operations (W = gap 63: behind   */  \
+        /* the last LDS-DMA piece; the walk's first step has only two) and stay in flight; everything older --  */  \
+        /* the pieces -- has retired                                                                            */  \
+        if (DS) {                                                                                                   \
+            if (FIRST) wait_vmem_le<2>();                                                                           \
+            else wait_vmem_le<4>();                                                                                 \
+            sw.p -= kDsTileBytes;                                                                                   \
+        } else {                                                                                                    \
+            glds_wait_all();                                                                                        \
+        }                                                                                                           \
         D4_LAP(6);                                                                                                  \
         block_sync_lds();                                                                                           \
         D4_LAP(7);                                                                                                  \
@@ -879,7 +1003,7 @@ LWM_DEVICE void attn_bwd_dkdv4_body(const AttnParams& p) {
 #undef D4_LAP2
 #undef LWM_D4_MASK
         // the last unit's products: its tiles are the second half of the PREVIOUS slot now (the registers moved on)
-        d4_drain<1>(cx, rg, dk, dv);
+        d4_drain<1, DS>(cx, rg, dk, dv, sw);
         d4_settle_acc(dk, dv);      // before the paths merge (hipcc reconciles the tuples by copies at the merge)
     }
 
@@ -890,6 +1014,7 @@ LWM_DEVICE void attn_bwd_dkdv4_body(const AttnParams& p) {
 #endif
     // The tiles leave as whole rows (attn_common.h, "epilogue staging"): the walk is over for every wave behind the
     // barrier, so the tile slots are free; a wave passes dK^T, then dV^T through its own 16 KiB of them.
+    if (DS) glds_wait_all();      // (the last dS stores: nothing of the walk is in flight behind this point)
     block_sync_lds();
     d4_store_tiles(p, lds + (uint32_t)wave * kEpiTileBytes, dk, dv, b, h, kbi * kD4BK + wave * 32, lane);
 #ifdef LWM_PROF
@@ -906,6 +1031,7 @@ LWM_DEVICE void attn_bwd_dkdv4_body(const AttnParams& p) {
 
 LWM_KERNEL(kD4Threads) void attn_bwd_dkdv4_kernel(AttnParams p) { attn_bwd_dkdv4_body<false>(p); }
 LWM_KERNEL(kD4Threads) void attn_bwd_dkdv4_meta_kernel(AttnParams p) { attn_bwd_dkdv4_body<true>(p); }
+LWM_KERNEL(kD4Threads) void attn_bwd_dkdv4_ds_kernel(AttnParams p) { attn_bwd_dkdv4_body<false, true>(p); }
 
 
 // ====================================================================================================== dQ
@@ -1445,5 +1571,208 @@ LWM_DEVICE void attn_bwd_dq4_body(const AttnParams& p) {
 
 LWM_KERNEL(kD4Threads) void attn_bwd_dq4_kernel(AttnParams p) { attn_bwd_dq4_body<false>(p); }
 LWM_KERNEL(kD4Threads) void attn_bwd_dq4_meta_kernel(AttnParams p) { attn_bwd_dq4_body<true>(p); }
+
+// ====================================================================================================== dQ from dS
+// The consumer of the dS hand-over (above): dQ = scale * dS K, ONE GEMM unit, no softmax, no masks -- a tile the dK/dV
+// walk did not visit holds only zeros and is simply not part of the sum, a masked element inside a visited tile was
+// stored as 0.  The kernel streams 2 bytes per 128 FLOP and is bound by HBM.
+//
+// Workgroup = 4 waves = 256 queries; a wave owns 64 query rows = one step st of the producer, i.e. ONE tile per key
+// step, private to the wave.  A key step = the 32 keys of one producer wave (key block kbi = step >> 2, wave step & 3),
+// ascending: the sum runs in key order, fixed, no atomics.  Computed transposed like the dQ kernel above:
+// dQ^T[db < 8][column tile] += K^T(db) dS^T, A = the transposed K fragments of the recompute kernel's Y phase, B = dS^T
+// read with the same instruction from the staged tile, 8 + 4 fragments for 32 MFMAs, the accumulators (32 tiles of
+// 16 x 16) in the accumulator file: 128 AGPRs.
+//
+// K (8 KiB per step, two 1-KiB pieces per wave, the q4 tile image) and the wave's tile (4 pieces) arrive by LDS-DMA
+// through a ring of kS4Slots slots, kS4Ahead steps ahead, behind counted waits; one barrier per step.
+//
+// The staged tile keeps the producer's 16-byte pieces whole and permutes them (on the SOURCE address of the DMA): the
+// piece of producer lane (c, g') stands at position 16 g' + (c ^ 8 (g' & 1)) of its 1-KiB unit-and-key-half.  The lane
+// t = 4 r + m of 16-lane group g of a transposed read points at key 4g + r and takes its four queries from the query
+// half m & 1 of producer group g' = 2 T + (m >> 1): a half-wave then reads 16 whole pieces at 16 distinct positions
+// mod 16 = every bank once (s4_image_ok).  Column t of the B operand -- and of the accumulator tiles [.., T] of the
+// unit -- is therefore query 16 ((t >> 2) & 1) + 4 (2 T + (t >> 3)) + (t & 3) of the unit, which is all the epilogue
+// needs to know; k-group g holds keys {4g .. 4g+3, 16+4g .. 16+4g+3} as in the other two kernels.
+constexpr int kS4BQ = 256;      // queries per workgroup
+constexpr int kS4BK = 32;       // keys per step
+constexpr int kS4Slots = 3;                // 72 KiB of LDS, 208 registers: TWO workgroups per CU -- one waits at its
+                                           // barrier while the other's pieces arrive (measured: 5.7 ms against 6.2 ms with
+                                           // four slots, three steps ahead and one workgroup per CU)
+constexpr int kS4Ahead = kS4Slots - 1;     // steps in flight
+constexpr int kS4KBytes = kS4BK * kRowBytes;                     // 8 KiB
+constexpr int kS4SlotBytes = kS4KBytes + 4 * kDsTileBytes;       // K tile | the four waves' dS tiles
+constexpr int kS4LdsBytes = kS4Slots * kS4SlotBytes;
+static_assert(kS4Ahead == 2 || kS4Ahead == 3, "the counted waits below leave one or two steps in flight");
+
+constexpr int s4_piece_pos(int c, int g) { return 16 * g + (c ^ ((g & 1) << 3)); }
+// byte offset, inside a 1-KiB unit-and-key-half, of the 8 bytes lane (t, g) of a transposed read of column tile T points at
+constexpr int s4_read_off(int t, int g, int T) { return 16 * s4_piece_pos(4 * g + (t >> 2), 2 * T + ((t & 3) >> 1)) + 8 * (t & 1); }
+constexpr bool s4_image_ok() {
+    for (int T = 0; T < 2; ++T)
+        for (int half = 0; half < 2; ++half) {
+            unsigned long long banks = 0;
+            for (int l = 32 * half; l < 32 * half + 32; ++l) {
+                const int a = s4_read_off(l & 15, l >> 4, T);
+                const unsigned long long b = 0x3ull << ((a >> 2) & 63);
+                if (banks & b) return false;
+                banks |= b;
+            }
+            if (banks != ~0ull) return false;
+        }
+    // the permutation is an involution on the 64 pieces (the DMA applies it to the source, the reads to the image)
+    for (int l = 0; l < 64; ++l)
+        if (s4_piece_pos(s4_piece_pos(l & 15, l >> 4) & 15, s4_piece_pos(l & 15, l >> 4) >> 4) != l) return false;
+    return true;
+}
+static_assert(s4_image_ok(), "a transposed read of the staged dS tile is bank-conflicted");
+
+// at most N vector-memory operations outstanding, N one of the sums a step's piece counts (0, 2 or 6) can make
+LWM_DEVICE void s4_wait_keep(int cnt) {
+    if (cnt >= 12) wait_vmem_le<12>();
+    else if (cnt >= 8) wait_vmem_le<8>();
+    else if (cnt >= 6) wait_vmem_le<6>();
+    else if (cnt >= 4) wait_vmem_le<4>();
+    else if (cnt >= 2) wait_vmem_le<2>();
+    else wait_vmem_le<0>();
+}
+
+// glds_load_b128 with the non-temporal hint (the tiles are read once; K is what the workgroups of an XCD share)
+#ifdef LWM_EMU
+LWM_DEVICE void s4_dma(const void* g, lds_t wave_base) { glds_load_b128(g, wave_base); }
+#else
+LWM_DEVICE void s4_dma(const void* g, lds_t wave_base) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(g), "s"(wave_base) : "memory");
+}
+#endif
+// a transposed fragment: the k-group's first four keys from `a`, its second four from `b`
+LWM_DEVICE bf16x8 s4_frag(lds_t a, lds_t b) {
+    const bf16x4 lo = lds_read_tr16(a), up = lds_read_tr16(b);
+    bf16x8 o;
+    o[0] = lo[0]; o[1] = lo[1]; o[2] = lo[2]; o[3] = lo[3];
+    o[4] = up[0]; o[5] = up[1]; o[6] = up[2]; o[7] = up[3];
+    return o;
+}
+
+LWM_DEVICE void attn_bwd_dq_ds_body(const AttnParams& p) {
+    const lds_t lds = dyn_lds();
+    const int tid = thread_idx();
+    const int wave = wave_uniform(tid >> 6), lane = tid & 63, l15 = lane & 15, g4 = lane >> 4;
+
+    // ---- block -> (q block, head, batch): the map of the dQ kernel
+    const int nqb = (p.Sq + kS4BQ - 1) / kS4BQ;
+    const int HB = p.H * p.B;
+    int lin = block_idx_x(), qbi, hb;
+    if ((HB & 7) == 0) {
+        int xcd = lin & 7, i = lin >> 3;
+        hb = xcd + 8 * (i / nqb);
+        qbi = nqb - 1 - (i % nqb);
+    } else {
+        hb = lin / nqb;
+        qbi = nqb - 1 - (lin % nqb);
+    }
+    const int b = hb / p.H, h = hb % p.H;
+    const char* kb = (const char*)(p.k + (int64_t)b * p.k_sb + (int64_t)h * p.k_sh);
+
+    // ---- the walk: this wave's tiles are the first n_w key steps, the workgroup walks those of its last query step
+    const int nst = p.Sq / kD4BQ, nkb = p.Sk / kD4BK;
+    const int64_t e = ds_diag(p.causal, p.q_start, p.k_start);
+    const int s_w = 4 * qbi + wave, s_last = 4 * qbi + 3 < nst ? 4 * qbi + 3 : nst - 1;
+    const int n_w = (int)ds_wave_steps(e, nst, nkb, s_w), n = (int)ds_wave_steps(e, nst, nkb, s_last);
+
+    f32x4 dq[2][16];            // [unit hq][2 db + T]: dQ^T rows 16 db + 4g + 0..3 of the query of column c (file header)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        dq[0][i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        dq[1][i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    }
+    q4_settle_acc(dq[0]);       // (compiler-written zeros: wait states before an MFMA reads them)
+    q4_settle_acc(dq[1]);
+
+    if (n > 0) {
+        // per-lane addresses: the K tile's transposed fragments (as the dQ kernel's Y phase), the dS tile's
+        uint32_t ka[8], da[2];
+#pragma unroll
+        for (int db = 0; db < 8; ++db) ka[db] = lds + q4_tile_off(4 * g4 + (l15 >> 2), 2 * db + ((l15 & 3) >> 1)) + (l15 & 1) * 8;
+#pragma unroll
+        for (int T = 0; T < 2; ++T) da[T] = lds + kS4KBytes + (uint32_t)wave * kDsTileBytes + (uint32_t)s4_read_off(l15, g4, T);
+        // DMA sources: the wave's two K pieces (rows 4 (wave + 4j) + (l >> 4), the swizzle on the source column) and the
+        // permuted piece of the tile
+        uint32_t vk[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int row = 4 * (wave + 4 * j) + g4;
+            vk[j] = (uint32_t)(((int64_t)row * p.k_ss + ((l15 ^ q4_swz(row)) << 3)) * 2);
+        }
+        const uint32_t vds = (uint32_t)s4_piece_pos(l15, g4) * 16;
+        const int64_t k_step_bytes = (int64_t)kS4BK * p.k_ss * 2;
+        // the cursor of the DMA: the row of tiles of key step `nxt` (it begins at the key block's first visited step)
+        const char* row_p = p.ds_ws + (int64_t)hb * ds_steps_before(e, nst, nkb) * 4 * kDsTileBytes;
+        int first = (int)ds_first_step(e, nst, 0);
+        const char* k_src = kb;
+        int nxt = 0;
+        uint32_t so_nxt = 0;        // byte offset of the slot of step nxt
+        auto issue = [&]() {        // the pieces of key step nxt -> its slot
+            const lds_t dst = lds + so_nxt;
+            glds_load_b128(k_src + vk[0], dst + (uint32_t)wave * 1024);
+            glds_load_b128(k_src + vk[1], dst + (uint32_t)(wave + 4) * 1024);
+            if (nxt < n_w) {
+                const char* t = row_p + (int64_t)(s_w - first) * kDsTileBytes + vds;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) s4_dma(t + 1024 * c, dst + kS4KBytes + (uint32_t)wave * kDsTileBytes + 1024 * c);
+            }
+            row_p += (int64_t)(nst - first) * kDsTileBytes;
+            if ((nxt & 3) == 3) first = (int)ds_first_step(e, nst, (nxt >> 2) + 1);
+            k_src += k_step_bytes;
+            so_nxt = so_nxt + kS4SlotBytes == (uint32_t)kS4LdsBytes ? 0u : so_nxt + (uint32_t)kS4SlotBytes;
+            ++nxt;
+        };
+        auto pieces = [&](int j) -> int { return j < n ? (j < n_w ? 6 : 2) : 0; };
+
+        for (int j = 0; j < kS4Ahead && j < n; ++j) issue();
+        s4_wait_keep(pieces(1) + (kS4Ahead == 3 ? pieces(2) : 0));
+        block_sync_lds();
+
+        // step i: the pieces of step i + kS4Ahead go out (their slot was read last in step i - 1), the products of step i,
+        // then step i + 1 must have landed for every wave: the younger steps stay in flight across the barrier
+        uint32_t so = 0;             // byte offset of the slot of step i
+        for (int i = 0; i < n; ++i) {
+            if (i + kS4Ahead < n) issue();
+            if (i < n_w) {
+                bf16x8 bf[2][2], af[8];
+#pragma unroll
+                for (int hq = 0; hq < 2; ++hq)
+#pragma unroll
+                    for (int T = 0; T < 2; ++T) bf[hq][T] = s4_frag(da[T] + so + 2048 * hq, da[T] + so + 2048 * hq + 1024);
+#pragma unroll
+                for (int db = 0; db < 8; ++db) af[db] = s4_frag(ka[db] + so, ka[db] + so + 16 * kRowBytes);
+#pragma unroll
+                for (int db = 0; db < 8; ++db)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) q4_mfma_o(dq[j >> 1][2 * db + (j & 1)], af[db], bf[j >> 1][j & 1]);
+            }
+            s4_wait_keep(pieces(i + 2) + (kS4Ahead == 3 ? pieces(i + 3) : 0));
+            block_sync_lds();
+            so = so + kS4SlotBytes == (uint32_t)kS4LdsBytes ? 0u : so + (uint32_t)kS4SlotBytes;
+        }
+        q4_settle_acc(dq[0]);       // before the paths merge, and before compiler-generated code reads the tuples
+        q4_settle_acc(dq[1]);
+    }
+
+    // ---- epilogue: the row-wise stores of the dQ kernel; column c of tile [.., T] of unit hq is this query
+    q4_settle_acc(dq[0]);
+    q4_settle_acc(dq[1]);
+    if (s_w < nst) {
+        const int row0 = s_w * kD4BQ + 16 * ((l15 >> 2) & 1) + 4 * (l15 >> 3) + (l15 & 3);
+        q4_store<0>(p, dq[0], b, h, row0, g4);
+        q4_store<1>(p, dq[0], b, h, row0 + 8, g4);
+        q4_store<0>(p, dq[1], b, h, row0 + 32, g4);
+        q4_store<1>(p, dq[1], b, h, row0 + 40, g4);
+    }
+}
+
+LWM_KERNEL(kD4Threads) void attn_bwd_dq_ds_kernel(AttnParams p) { attn_bwd_dq_ds_body(p); }
 
 }  // namespace lwm

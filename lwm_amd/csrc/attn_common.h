@@ -78,6 +78,8 @@ struct AttnParams {
     // block-sparsity hints (packed sequences), see include/lwm_hip.h
     const int32_t* segb_q;
     const int32_t* segb_k;
+    // backward only: the dS hand-over workspace (attn_bwd64.h, "dS hand-over"), null = none
+    char* ds_ws;
 };
 
 // ---- position maps (see AttnParams): everything below is wave-uniform scalar arithmetic over the piece tables in the

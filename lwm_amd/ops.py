@@ -449,9 +449,20 @@ def _acc_shape(B, Sq, H, D, head_major):
     return (B, H, Sq, D) if head_major else (B, Sq, H, D)
 
 
+# ---- dS hand-over (include/lwm_hip.h, LwmAttnArgs::ds_ws): attn_bwd_dkdv_block stores its dS in the workspace and
+# attn_bwd_dq_block, called after it with the same arguments, computes dq from them in one GEMM (ring.py allots it)
+def _set_ds_ws(a, ds_ws, like):
+    if ds_ws is None:
+        return
+    if not torch.is_tensor(ds_ws) or ds_ws.device != like.device or ds_ws.dtype != torch.uint8 or not ds_ws.is_contiguous():
+        raise ValueError(f"ds_ws: expected a contiguous uint8 tensor on {like.device}")
+    a.ds_ws, a.ds_ws_bytes = ds_ws.data_ptr(), ds_ws.numel()
+
+
 def attn_bwd_dq_block(q, k, v, dout, lse, delta, *, q_start=0, k_start=0, causal=True,
                       seg_q=None, seg_k=None, key_valid=None, scale=None, dq=None, dq_acc=None,
-                      carry_in=False, final=True, acc_head_major=False, q_piece2=None, k_piece2=None):
+                      carry_in=False, final=True, acc_head_major=False, q_piece2=None, k_piece2=None, ds_ws=None):
+    """ds_ws: the workspace attn_bwd_dkdv_block has just filled for the same arguments (dS hand-over), or None"""
     B, Sq, H, D = q.shape
     a = _bwd_base(q, k, v, dout, lse, delta,
                   dict(q_start=q_start, k_start=k_start, causal=causal, seg_q=seg_q, seg_k=seg_k,
@@ -467,6 +478,7 @@ def attn_bwd_dq_block(q, k, v, dout, lse, delta, *, q_start=0, k_start=0, causal
     a.carry_in = int(bool(carry_in))
     a.final_out = int(bool(final))
     _set_hints(a)
+    _set_ds_ws(a, ds_ws, q)
     L = lib()
     _capi.check(L, _entry(L, "lwm_attn_bwd_dq", q.dtype)(C.byref(a), _stream_ptr()), "lwm_attn_bwd_dq")
     return dq if final else dq_acc
@@ -474,7 +486,8 @@ def attn_bwd_dq_block(q, k, v, dout, lse, delta, *, q_start=0, k_start=0, causal
 
 def attn_bwd_dkdv_block(q, k, v, dout, lse, delta, *, q_start=0, k_start=0, causal=True,
                         seg_q=None, seg_k=None, key_valid=None, scale=None, dk=None, dv=None,
-                        dk_acc=None, dv_acc=None, carry_in=False, final=True, q_piece2=None, k_piece2=None):
+                        dk_acc=None, dv_acc=None, carry_in=False, final=True, q_piece2=None, k_piece2=None, ds_ws=None):
+    """ds_ws: a uint8 workspace of lwm_attn_bwd_ds_bytes bytes: the kernel also stores its dS there (dS hand-over), or None"""
     B, Sk, H, D = k.shape
     a = _bwd_base(q, k, v, dout, lse, delta,
                   dict(q_start=q_start, k_start=k_start, causal=causal, seg_q=seg_q, seg_k=seg_k,
@@ -495,6 +508,7 @@ def attn_bwd_dkdv_block(q, k, v, dout, lse, delta, *, q_start=0, k_start=0, caus
     a.carry_in = int(bool(carry_in))
     a.final_out = int(bool(final))
     _set_hints(a)
+    _set_ds_ws(a, ds_ws, q)
     L = lib()
     _capi.check(L, _entry(L, "lwm_attn_bwd_dkdv", q.dtype)(C.byref(a), _stream_ptr()), "lwm_attn_bwd_dkdv")
     return (dk, dv) if final else (dk_acc, dv_acc)

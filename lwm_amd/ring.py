@@ -234,6 +234,42 @@ class SingleComm:
 
 
 # ----------------------------------------------------------------- block ops
+# dS hand-over (include/lwm_hip.h, LwmAttnArgs::ds_ws): the dk/dv launch stores its dS in a workspace and the dq launch
+# that follows it with the same arguments computes dq from them in one GEMM.
+# LWM_BWD_DS_MB = the most a workspace may take, in MiB (0: no hand-over).  The cost is memory: B * H * Sq * Sk bytes for a
+# causal square block, twice that without the mask -- 32 GiB at B = 1, H = 32, S = 32768, which the default admits.
+DS_BUDGET_MB_DEFAULT = 40960
+_ds_cache = {}      # device index -> (bytes, uint8 tensor): one workspace per device, reused by every layer
+
+
+def _ds_workspace(q, k, *, q_start=0, k_start=0, causal=True, seg_k=None, key_valid=None):
+    """The workspace of the dS hand-over for this (query block, K/V block) pair, or None when the pair does not take
+    it: not bf16, segment ids or padded keys, a shape lwm_attn_bwd_ds_bytes refuses, more bytes than LWM_BWD_DS_MB
+    admits or than the device has left.  Cached per device; a call with another size frees the old one first."""
+    if q.dtype != torch.bfloat16 or not q.is_cuda or seg_k is not None or key_valid is not None:
+        return None
+    budget = float(os.environ.get("LWM_BWD_DS_MB", DS_BUDGET_MB_DEFAULT)) * (1 << 20)
+    if budget <= 0:
+        return None
+    B, Sq, H, _ = q.shape
+    need = int(_ops.lib().lwm_attn_bwd_ds_bytes(B, H, Sq, k.shape[1], int(bool(causal)), int(q_start), int(k_start)))
+    if need <= 0 or need > budget:
+        return None
+    idx = q.device.index if q.device.index is not None else torch.cuda.current_device()
+    have = _ds_cache.get(idx)
+    if have is not None and have[0] == need:
+        return have[1]
+    _ds_cache.pop(idx, None)       # the shape changed: the old workspace goes before the new one is asked for
+    have = None
+    try:
+        ws = torch.empty(need, dtype=torch.uint8, device=q.device)
+    except torch.OutOfMemoryError:
+        return None
+    _ds_cache[idx] = (need, ws)
+    return ws
+
+
+# ----------------------------------------------------------------- block ops
 class HipBlockOps:
     """The product backend: hand-written HIP kernels through the C ABI."""
 
@@ -243,6 +279,7 @@ class HipBlockOps:
     bwd_delta = staticmethod(_ops.attn_bwd_delta)
     bwd_dq = staticmethod(_ops.attn_bwd_dq_block)
     bwd_dkdv = staticmethod(_ops.attn_bwd_dkdv_block)
+    ds_workspace = staticmethod(_ds_workspace)
     cast = staticmethod(_ops.cast_f32_to_bf16)
     sum_cast = staticmethod(_ops.sum_f32_to_bf16)
     fwd_splitk = staticmethod(_ops.attn_fwd_splitk)
@@ -259,8 +296,10 @@ class HipBlockOps:
 
 
 # The backward is deterministic: lwm_attn_bwd_delta + lwm_attn_bwd_dkdv + lwm_attn_bwd_dq, no atomics, fixed summation
-# orders (7 GEMM units executed: S and dP are recomputed by the dq kernel).  A 5-unit form that stored bf16 dq partials
-# was measured in rounds 2-3 and retired in round 4 (profiles/r04_backward.md).
+# orders.  9 GEMM units are executed for the 7 of the algorithm where the dq kernel recomputes S and dP; a single block
+# (ring_backward, n == 1) executes 7: the dk/dv kernel hands its dS to the dq kernel through a workspace in HBM
+# (_ds_workspace, LWM_BWD_DS_MB).  A 5-unit form that stored bf16 dq partials was measured in rounds 2-3 and
+# retired in round 4 (profiles/r04_backward.md).
 
 
 # ----------------------------------------------------------------- helpers
@@ -614,8 +653,13 @@ def ring_backward(block, comm, q, k, v, out, lses, dout, *, layout, causal=True,
         sq, sk, kv = masks(qs, qs)
         kw = dict(q_start=qs[2], k_start=qs[2], causal=causal, seg_q=sq, seg_k=sk, key_valid=kv,
                   scale=scale)
-        dk, dv = block.bwd_dkdv(q, k, v, dout, lses[0], deltas[0], final=True, **kw)
-        dq = block.bwd_dq(q, k, v, dout, lses[0], deltas[0], final=True, **kw)
+        # dS hand-over: with a workspace the dq launch reads the dS the dk/dv launch has just stored (same arguments,
+        # same stream, this order); a backend without one, or a call that does not take it, runs the recompute kernels
+        ws = getattr(block, "ds_workspace", None)
+        ws = None if ws is None else ws(q, k, q_start=qs[2], k_start=qs[2], causal=causal, seg_k=sk, key_valid=kv)
+        hand = {} if ws is None else dict(ds_ws=ws)
+        dk, dv = block.bwd_dkdv(q, k, v, dout, lses[0], deltas[0], final=True, **kw, **hand)
+        dq = block.bwd_dq(q, k, v, dout, lses[0], deltas[0], final=True, **kw, **hand)
         return dq, dk, dv
 
     if _is_mesh(comm):

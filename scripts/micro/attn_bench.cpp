@@ -1,7 +1,8 @@
 // attn_bench.cpp -- times the attention kernels of one layer through the C ABI, without Python:
 //   attn_bench <liblwm_hip.so> [S=32768] [H=32] [reps=3]
 // One line per library: HIP-event ms per launch of lwm_attn_fwd, lwm_attn_bwd_delta, _dkdv and _dq, and mean |x| checksums
-// of dq / dk / dv, so that a timing variant that breaks a result is visible.  scripts/gpu_ab.sh sweeps variant builds
+// of dq / dk / dv, so that a timing variant that breaks a result is visible.  A library that has the dS hand-over
+// (lwm_attn_bwd_ds_bytes) is timed a second time with the workspace: `dkdv+ds` stores dS, `dq<-ds` consumes it.  scripts/gpu_ab.sh sweeps variant builds
 // (scripts/ab_build.sh) with it in one GPU call.  LWM_PROF_DUMP=1 with a -DLWM_PROF build prints the s_memtime laps of
 // the dK/dV kernel (attn_bwd64.h), LWM_PROF_DUMP=-1 those of the forward (attn_fwd64.h).
 // Build: hipcc -O2 --offload-arch=gfx950 -I include -o scripts/micro/attn_bench scripts/micro/attn_bench.cpp -ldl
@@ -170,5 +171,23 @@ int main(int argc, char** argv) {
     const float ms_dq = time_ms([&] { must(bdq(&a, nullptr), "dq"); });
     printf("%-34s S=%d H=%d  fwd %.3f  delta %.3f  dkdv %.3f  dq %.3f ms   |dq| %.6f |dk| %.6f |dv| %.6f\n", argv[1], S, H, ms_fwd,
            ms_delta, ms_dkdv, ms_dq, checksum(dq), checksum(dk), checksum(dv));
+    auto ds_bytes = (int64_t (*)(int32_t, int32_t, int32_t, int32_t, int32_t, int64_t, int64_t))dlsym(lib, "lwm_attn_bwd_ds_bytes");
+    const int64_t need = ds_bytes ? ds_bytes(1, H, S, S, 1, 0, 0) : 0;
+    if (need > 0 && !getenv("LWM_BENCH_NO_DS")) {
+        void* ws = nullptr;
+        CK(hipMalloc(&ws, (size_t)need));
+        CK(hipMemset(dq, 0, n * 2));
+        CK(hipMemset(dk, 0, n * 2));
+        CK(hipMemset(dv, 0, n * 2));
+        a.ds_ws = ws;
+        a.ds_ws_bytes = need;
+        const float ms_dkdv2 = time_ms([&] { must(bdkdv(&a, nullptr), "dkdv+ds"); });
+        const float ms_dq2 = time_ms([&] { must(bdq(&a, nullptr), "dq<-ds"); });
+        printf("%-34s S=%d H=%d  workspace %.2f GiB  dkdv+ds %.3f  dq<-ds %.3f ms   |dq| %.6f |dk| %.6f |dv| %.6f\n", argv[1], S, H,
+               (double)need / (1 << 30), ms_dkdv2, ms_dq2, checksum(dq), checksum(dk), checksum(dv));
+        a.ds_ws = nullptr;
+        a.ds_ws_bytes = 0;
+        CK(hipFree(ws));
+    }
     return 0;
 }
