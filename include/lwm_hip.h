@@ -842,6 +842,21 @@ typedef struct LwmConvArgs {
 } LwmConvArgs;
 int lwm_conv2d_nhwc_f32(const LwmConvArgs* args, void* stream);
 
+/* The same convolution in the opt-in second precision (lwm_version() >= 620): operands rounded to bf16 (round to
+ * nearest even), products exact, f32 accumulation, on v_mfma_f32_32x32x16_bf16.  NOT bit-exact with the oracle; the
+ * contract is |y - y64| <= (K + 2) 2^-23 (sum |bf16(x) bf16(w)| + |bias| + |residual|), K = KH KW Cin, y64 the fp64
+ * convolution of the rounded operands, and exact results wherever every partial sum is an integer below 2^24.
+ * The struct is the one above with ONE difference: `w` points at the PACKED kernel,
+ *     bf16 [KH*KW][Cin/8][Cout][8]:  element (kh, kw, ci, co) at (((kh*KW + kw) * Cin/8 + ci/8) * Cout + co) * 8 + ci%8
+ * (a lane's B fragment of the matrix instruction, 8 consecutive input channels of one output channel, is one 16-byte
+ * load; lwm_amd.ops.conv_pack_bf16 builds it from the HWIO kernel).  x, bias, residual and y stay f32: x is rounded
+ * inside the kernel, on its way into LDS.  Out-of-image taps are exact zeros and are never read; the order of the sum
+ * depends on the launch geometry alone: the same call twice gives the same bits, and an image's bits do not depend on
+ * the rest of the batch.  Normal numbers only: subnormal and non-finite operands are outside the contract.
+ * Cin % 32 == 0 and Cout % 32 == 0 (every VQGAN layer but the two 3-channel ends), otherwise LWM_EUNSUPPORTED;
+ * null / misaligned / bad-dimension arguments are refused as by the f32 entry. */
+int lwm_conv2d_nhwc_bf16(const LwmConvArgs* args, void* stream);
+
 /* flax nn.GroupNorm (num_groups G, eps, affine) over x [B,HW,C], optionally
  * followed by nn.silu (lwm/vqgan.py:161-162,181-182,251-255).  `workspace` is
  * caller-owned device memory of lwm_groupnorm_workspace_bytes() bytes (f64

@@ -291,6 +291,7 @@ PROTOTYPES = {
     "lwm_cast_f32_to_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "lwm_sum_f32_to_bf16": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "lwm_conv2d_nhwc_f32": (C.c_int, [C.POINTER(LwmConvArgs), C.c_void_p]),
+    "lwm_conv2d_nhwc_bf16": (C.c_int, [C.POINTER(LwmConvArgs), C.c_void_p]),
     "lwm_groupnorm_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
     "lwm_groupnorm_silu_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_int64, C.c_int32, C.c_int32,
                                                             C.c_float, C.c_int32, C.c_void_p]),

@@ -245,10 +245,25 @@ def load_tokenizer(name: str):
                          f"with the LLaMA tokenizer files, or --tokenizer=synthetic for a byte-level stand-in")
 
 
+def parse_vqgan_precision(text):
+    """LWM_VQGAN_PRECISION -> "f32" (unset, empty or f32) or "bf16", any letter case; anything else ends the run, naming
+    the variable"""
+    p = (text or "f32").lower()
+    if p not in ("f32", "bf16"):
+        raise SystemExit(f"LWM_VQGAN_PRECISION={text!r}: 'f32' (the default: the bit-exact tokeniser), 'bf16' or unset")
+    return p
+
+
 def load_vqgan(path: str, seed: int):
+    """The tokeniser of vision_chat and vision_generation.  LWM_VQGAN_PRECISION=bf16: its convolutions round their
+    operands to bf16 (VQGAN(precision="bf16"): faster, codes and pixels move a little -- README.md); the reference's
+    flag sets have no such flag, so it is an environment variable.  Unset or f32: the bit-exact route."""
     from ..vqgan import VQGAN, VQGANConfig, random_params
+    precision = parse_vqgan_precision(os.environ.get("LWM_VQGAN_PRECISION", ""))
+    if precision != "f32":
+        note(f"LWM_VQGAN_PRECISION={precision}: VQGAN convolutions on bf16 operands with f32 accumulation")
     if path:
-        return VQGAN(path, replicate=False)
+        return VQGAN(path, replicate=False, precision=precision)
     note("no --vqgan_checkpoint: VQGAN with seeded random weights")
     cfg = VQGANConfig.get_default_config()
-    return VQGAN(params=random_params(cfg, seed), config=cfg)
+    return VQGAN(params=random_params(cfg, seed), config=cfg, precision=precision)

@@ -998,7 +998,7 @@ int lwm_adamw_step(const LwmAdamWArgs* a, void* stream) {
 int lwm_adamw_chunk(void) { return lwm::kAdamWChunk; }
 
 const char* lwm_last_error(void) { return lwm::g_err; }
-int lwm_version(void) { return 610; }
+int lwm_version(void) { return 620; }
 int lwm_sizeof(int which) {
     return which == 0 ? (int)sizeof(LwmAttnArgs) : which == 1 ? (int)sizeof(LwmConvArgs) : which == 2 ? (int)sizeof(LwmRingArgs) : which == 3 ? (int)sizeof(LwmGemvArgs) : which == 4 ? (int)sizeof(LwmSampleArgs) : which == 5 ? (int)sizeof(LwmKv8DecodeArgs) : which == 6 ? (int)sizeof(LwmKv8PrefillArgs) : which == 7 ? (int)sizeof(LwmAdamWArgs) : which == 8 ? (int)sizeof(LwmAdamWTensor) : which == 9 ? (int)sizeof(LwmGemvW8Args) : which == 10 ? (int)sizeof(LwmKv4DecodeArgs) : which == 11 ? (int)sizeof(LwmGemvW4Args) : which == 12 ? (int)sizeof(LwmFramesArgs) : -1;
 }

@@ -3,6 +3,7 @@
 // and tests/emu/lwm_emu.cpp (host emulation, test-only).
 
 #include "frames.h"
+#include "vqgan_conv_bf16.h"
 
 namespace lwm {
 
@@ -61,8 +62,11 @@ static int gn_slices(int64_t HW) {
 
 extern "C" {
 
-int lwm_conv2d_nhwc_f32(const LwmConvArgs* a, void* stream) {
+// what the two convolution entries check alike, and their ConvParams; B == 0 leaves p->M == 0: nothing to launch
+static int conv_params(const LwmConvArgs* a, lwm::ConvParams* pp) {
     using namespace lwm;
+    ConvParams& p = *pp;
+    p.M = 0;
     if (!a) return fail(LWM_EINVAL, "%s", "conv: args is null");
     if (!a->x || !a->w || !a->y) return fail(LWM_EINVAL, "%s", "conv: null tensor");
     if (a->B < 0 || a->Hin <= 0 || a->Win <= 0 || a->Cin <= 0 || a->Cout <= 0 || a->KH <= 0 ||
@@ -76,14 +80,21 @@ int lwm_conv2d_nhwc_f32(const LwmConvArgs* a, void* stream) {
     // (the kernels address a pixel inside its image with 32 bits; the image base is 64-bit)
     if ((int64_t)a->Hin * a->Win * a->Cin >= (1LL << 31) || (int64_t)a->Ho * a->Wo * a->Cout >= (1LL << 31))
         return fail(LWM_EUNSUPPORTED, "%s: one image holds 2^31 elements or more (H x W = %ld x %ld)", "conv", (long)a->Hin, (long)a->Win);
-    ConvParams p;
     p.x = a->x; p.w = a->w; p.bias = a->bias; p.res = a->residual; p.y = a->y;
     p.B = a->B; p.Hin = a->Hin; p.Win = a->Win; p.Cin = a->Cin; p.Cout = a->Cout;
     p.KH = a->KH; p.KW = a->KW; p.stride = a->stride; p.pad = a->pad; p.up_shift = a->up_shift;
     p.Ho = a->Ho; p.Wo = a->Wo; p.clip = a->clip ? 1 : 0;
     p.M = (int64_t)a->B * a->Ho * a->Wo;
+    if (((p.M + 31) / 32) * (((int64_t)p.Cout + 31) / 32) > 0x7fffffffLL) return fail(LWM_EINVAL, "%s", "conv: grid too large");
+    return LWM_OK;
+}
+
+int lwm_conv2d_nhwc_f32(const LwmConvArgs* a, void* stream) {
+    using namespace lwm;
+    ConvParams p;
+    if (const int r = conv_params(a, &p)) return r;
+    if (!p.M) return LWM_OK;
     auto tiles = [&](int bm, int bn) { return ((p.M + bm - 1) / bm) * ((p.Cout + bn - 1) / bn); };
-    if (tiles(32, 32) > 0x7fffffffLL) return fail(LWM_EINVAL, "%s", "conv: grid too large");
     const bool vec = (p.Cin % 4 == 0) && (p.Cout % 4 == 0);
     // 3x3 stride-1 SAME (optionally over the x2-upsampled image) with 128 / 256 input channels: halo patch
     // resident in LDS (vqgan_conv.h::conv_patch_body)
@@ -129,6 +140,28 @@ int lwm_conv2d_nhwc_f32(const LwmConvArgs* a, void* stream) {
                         ConvCfg<2, 2, 2, 2>::LDS_BYTES, stream, p)
                : launch("conv_igemm_128x128_g", conv_igemm_128x128_g, tiles(128, 128), 256,
                         ConvCfg<2, 2, 2, 2>::LDS_BYTES, stream, p);
+}
+
+int lwm_conv2d_nhwc_bf16(const LwmConvArgs* a, void* stream) {
+    using namespace lwm;
+    ConvParams p;      // (p.w: the bf16 pack, vqgan_conv_bf16.h)
+    if (const int r = conv_params(a, &p)) return r;
+    if (a->Cin % 32 || a->Cout % 32)
+        return fail(LWM_EUNSUPPORTED, "%s: Cin=%ld Cout=%ld (need Cin %% 32 == 0 and Cout %% 32 == 0; lwm_conv2d_nhwc_f32 serves the rest)",
+                    "conv_bf16", (long)a->Cin, (long)a->Cout);
+    if (!p.M) return LWM_OK;
+    // (its staging offsets are 32-bit, relative to the image of a tile's first pixel: the images a 128-pixel tile can
+    //  reach; its B offsets are 32-bit inside the pack)
+    if ((128 / ((int64_t)p.Ho * p.Wo) + 2) * ((int64_t)p.Hin * p.Win * p.Cin * 4) >= 0xE0000000LL ||
+        (int64_t)p.KH * p.KW * p.Cin * p.Cout * 2 >= 0xE0000000LL)
+        return fail(LWM_EUNSUPPORTED, "%s: an image or the packed kernel is too large for 32-bit staging offsets (H x W = %ld x %ld)",
+                    "conv_bf16", (long)a->Hin, (long)a->Win);
+    auto tiles = [&](int bm, int bn) { return ((p.M + bm - 1) / bm) * ((p.Cout + bn - 1) / bn); };
+    if (p.Cout == 32)
+        return launch("conv16_igemm_128x32", conv16_igemm_128x32, tiles(128, 32), 256, Conv16T128x32::LDS_BYTES, stream, p);
+    if (p.Cout <= 64 || tiles(128, 128) < device_cu_count())     // narrow, or too few workgroups for the machine
+        return launch("conv16_igemm_64x64", conv16_igemm_64x64, tiles(64, 64), 256, Conv16T64x64::LDS_BYTES, stream, p);
+    return launch("conv16_igemm_128x128", conv16_igemm_128x128, tiles(128, 128), 256, Conv16T128x128::LDS_BYTES, stream, p);
 }
 
 int64_t lwm_groupnorm_workspace_bytes(int32_t B, int64_t HW, int32_t C, int32_t G) {

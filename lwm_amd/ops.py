@@ -715,3 +715,7 @@ def sample_tokens(logits, *, temperature, top_k, seed, step_dev=None, step=0, st
     L = lib()
     _capi.check(L, L.lwm_sample_tokens(C.byref(a), _stream_ptr()), "lwm_sample_tokens")
     return tokens_out
+
+
+# the bf16 flavour of conv2d_nhwc, with the pack of its kernel (lwm_conv2d_nhwc_bf16): a module of its own
+from .vqgan_bf16 import ConvPackBF16, conv2d_nhwc_bf16, conv_pack_bf16      # noqa: E402,F401

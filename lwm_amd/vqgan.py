@@ -138,11 +138,17 @@ def _to_device(tree, device):
 
 
 class VQGAN:
-    def __init__(self, vqgan_checkpoint="", replicate=False, *, params=None, config=None, device=None):
+    def __init__(self, vqgan_checkpoint="", replicate=False, *, params=None, config=None, device=None, precision="f32"):
         """`vqgan_checkpoint`: pickle of the flax parameter tree (lwm/vqgan.py:19), or pass
         `params` (the same nested dict) directly.  `replicate` (pmap over local devices in
         the reference, :20-24) is accepted for signature compatibility: frames are
-        independent, so multi-GPU use is one VQGAN per process ("replicas only")."""
+        independent, so multi-GPU use is one VQGAN per process ("replicas only").
+        `precision`: "f32" (the default: every convolution on the exact-f32 matrix instruction, bit-exact with the
+        oracle) or "bf16" (opt-in: the convolutions with Cin % 32 == 0 and Cout % 32 == 0 -- all but the two 3-channel
+        ends -- round their operands to bf16 and accumulate in f32, ops.conv2d_nhwc_bf16; GroupNorm + SiLU, the
+        quantiser, the codebook and every activation in memory stay f32)."""
+        if precision not in ("f32", "bf16"):
+            raise ValueError(f"VQGAN: precision={precision!r}: 'f32' (the default) or 'bf16'")
         if params is None:
             assert vqgan_checkpoint != ""
             from .weights import load_pickle_tree      # also reads pickles written from jax arrays
@@ -156,6 +162,20 @@ class VQGAN:
         self._codebook = self.params["quantize"]["embeddings"]
         self._se = ops.vq_sqnorm(self._codebook)
         self._ws = None
+        self.precision = precision
+        if precision == "bf16":
+            # every eligible kernel packed once (the f32 kernels stay: the 3-channel ends take them), by kernel tensor
+            self._packs = {}
+            self._pack_tree(self.params)
+            self._conv = self._conv_bf16
+
+    def _pack_tree(self, tree):
+        k = tree.get("kernel")
+        if k is not None and not isinstance(k, dict) and k.dim() == 4 and k.shape[2] % 32 == 0 and k.shape[3] % 32 == 0:
+            self._packs[id(k)] = ops.conv_pack_bf16(k)
+        for v in tree.values():
+            if isinstance(v, dict):
+                self._pack_tree(v)
 
     # ---- building blocks
     def _gn_silu(self, p, x):
@@ -169,6 +189,12 @@ class VQGAN:
     @staticmethod
     def _conv(p, x, **kw):
         return ops.conv2d_nhwc(x, p["kernel"], p["bias"], **kw)
+
+    def _conv_bf16(self, p, x, **kw):
+        pack = self._packs.get(id(p["kernel"]))
+        if pack is None:
+            return ops.conv2d_nhwc(x, p["kernel"], p["bias"], **kw)
+        return ops.conv2d_nhwc_bf16(x, pack, p["bias"], **kw)
 
     def _resnet(self, p, x):
         h = self._gn_silu(p["GroupNorm_0"], x)
