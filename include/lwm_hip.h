@@ -494,6 +494,95 @@ typedef struct LwmKv4DecodeArgs {
 } LwmKv4DecodeArgs;
 int lwm_attn_decode_kv4(const LwmKv4DecodeArgs* args, void* stream);
 
+/* ------------------------------------------------------------------ 6-bit KV cache (lwm_version() >= 630)
+ * The cache in the OCP MXFP6 format: e2m3 codes with one e8m0 scale byte per block of 32 elements.  100 bytes per
+ * (row, head) against 256 for bf16, 132 for the 8-bit cache and 68 for the 4-bit one: 0.39 of the bf16 cache's bytes,
+ * in memory and per decode step.  Per layer four tensors:
+ *   cached_key, cached_value          uint8 (B, max_length, H, 96): head element d belongs to block d / 32; a block is
+ *                                     24 bytes and a head row its four blocks in order; element j of a block occupies
+ *                                     bits [6j, 6j + 6) of the block's 24 bytes read as one little-endian 192-bit
+ *                                     integer (the order in which v_cvt_scalef32_pk32_f32_fp6 reads its six registers);
+ *                                     heads of a row contiguous;
+ *   key_scale_e8m0, value_scale_e8m0  uint8 (B, max_length, H, 4): as in the 4-bit cache, one e8m0 byte b per block,
+ *                                     the scale 2^(b - 127).  (The two caches differ in the last dimension of
+ *                                     cached_key: 96 here, 64 there.)
+ * e2m3: the sign in bit 5, the exponent (bias 1) in bits 4-3, the mantissa in bits 2-0.  For the magnitude code
+ * c = 0..31: c / 8 where c < 8, else (1 + (c & 7) / 8) * 2^((c >> 3) - 1); the largest magnitude is 7.5.  Magnitudes
+ * are monotone in c and the mantissa's last bit is the code's last bit, so IEEE round-to-nearest-even is "ties to the
+ * even code".
+ * One block (32 bf16 values x): amax = max |x|; s = the smallest power of two with amax / s <= 7.5, its biased
+ * exponent clamped to [1, 254] (s >= 2^-126; byte 255 is never written), s = 1 (byte 127) when amax == 0;
+ * q = e2m3(x / s), round to nearest, ties to the even code (x / s is exact in f32 and in range: nothing saturates;
+ * -0 keeps its sign).  This is the 4-bit cache's rule with 7.5 in place of 6.  q * s has at most 4 significant bits:
+ * it is exactly representable in bf16, a normal number whenever s >= 2^-123.  Non-finite inputs are not supported, nor
+ * is a block whose amax reaches 1.9375 * 2^127 (about 3.30e38): its largest element rounds up to 2^128, past the top of
+ * bf16.  Away from the lower clamp: |x - q s| <= s / 4 and s < amax / 3.75, hence |x - q s| < amax / 15;
+ * |x - q s| <= 2^-4 |x| for |x| >= s; and element by element the error is never larger than the 4-bit cache's on the
+ * same block.
+ *
+ * lwm_kv6_cache_write / _at: the arguments of lwm_kv4_cache_write / _at (row_elems = H * 128; cache and scale batch
+ * strides in bytes, src strides in bf16 elements); rows of a batch entry are contiguous (H * 96 and H * 4 bytes).
+ * src 16-byte aligned, cache 8-byte aligned, scale 4-byte aligned; otherwise LWM_EINVAL. */
+int lwm_kv6_cache_write(void* cache, const void* src, int32_t B, int64_t cache_stride_b,
+                        int64_t src_stride_b, int64_t dst_row0, int64_t src_row0, int64_t nrows,
+                        int32_t row_elems, void* scale, int64_t scale_stride_b, int32_t H, void* stream);
+int lwm_kv6_cache_write_at(void* cache, const void* src, int32_t B, int64_t cache_stride_b,
+                           int64_t src_stride_b, const int32_t* dst_row0_dev, int64_t row_offset,
+                           int64_t cache_rows, int64_t src_row0, int64_t nrows, int32_t row_elems,
+                           void* scale, int64_t scale_stride_b, int32_t H, void* stream);
+
+/* Cached-decode attention (one query per batch row) over that cache: the contract of lwm_attn_decode_kv4 (masked keys
+ * contribute nothing whatever their bytes and scale bytes hold; a row with nothing visible gives (0, -inf); the score of
+ * a key is the sum over its four blocks of scale_b * (q_b . k_b)).  D = 128; q and out_acc 16-byte aligned; the cache
+ * rows (k/v_stride_* in bytes, a head is 96 contiguous bytes) 8-byte aligned, pointers and strides; scale strides in
+ * bytes, the 4 bytes of a head and the H heads of a row contiguous; 0 <= k_splits <= 4096.  Anything else is LWM_EINVAL
+ * with a message. */
+typedef struct LwmKv6DecodeArgs {
+    LwmTensor4 q;                   /* bf16 (B,1,H,D) */
+    const void* k;                  /* e2m3 blocks (B,Sk,H,96) */
+    const void* v;
+    int64_t k_stride_b, k_stride_s, k_stride_h;
+    int64_t v_stride_b, v_stride_s, v_stride_h;
+    const void* k_scale;            /* e8m0 bytes (B,Sk,H,4) */
+    const void* v_scale;
+    int64_t k_scale_stride_b, k_scale_stride_s;
+    int64_t v_scale_stride_b, v_scale_stride_s;
+    const uint8_t* dense_mask;      /* (B,Sk) u8, nonzero = visible; NULL = all visible */
+    int64_t mask_stride_b;
+    int32_t B, Sk, H, D;
+    float scale;                    /* softmax scale, > 0 */
+    int32_t k_splits;
+    float* out_acc;
+    float* lse_acc;
+} LwmKv6DecodeArgs;
+int lwm_attn_decode_kv6(const LwmKv6DecodeArgs* args, void* stream);
+
+/* A BLOCK of Sq queries over that cache: the contract of lwm_attn_prefill_kv8 (key j < Sk visible to query i iff
+ * j <= q_start + i and key_valid[b, j] != 0; lwm_attn_fwd's split-K kernel with the staging replaced; the partials bit
+ * for bit those of lwm_attn_fwd with final_out = 0 and the same k_splits >= 2 over a bf16 copy of the dequantised cache;
+ * masked rows and rows at or past Sk contribute nothing whatever their bytes and scale bytes hold).  D = 128, Sq >= 1,
+ * Sk >= 1, 0 <= k_splits <= 4096; alignment and strides as lwm_attn_decode_kv6; key_valid_stride_b in bytes. */
+typedef struct LwmKv6PrefillArgs {
+    LwmTensor4 q;                   /* bf16 (B,Sq,H,D) */
+    const void* k;                  /* e2m3 blocks (B,Sk,H,96) */
+    const void* v;
+    int64_t k_stride_b, k_stride_s, k_stride_h;
+    int64_t v_stride_b, v_stride_s, v_stride_h;
+    const void* k_scale;            /* e8m0 bytes (B,Sk,H,4) */
+    const void* v_scale;
+    int64_t k_scale_stride_b, k_scale_stride_s;
+    int64_t v_scale_stride_b, v_scale_stride_s;
+    const uint8_t* key_valid;       /* (B,Sk) u8, nonzero = valid; NULL = all valid */
+    int64_t key_valid_stride_b;
+    int32_t B, Sq, Sk, H, D;
+    int64_t q_start;                /* position of query row 0 (= the cache index the block was written at) */
+    float scale;                    /* softmax scale, > 0 */
+    int32_t k_splits;
+    float* out_acc;
+    float* lse_acc;
+} LwmKv6PrefillArgs;
+int lwm_attn_prefill_kv6(const LwmKv6PrefillArgs* args, void* stream);
+
 /* Elementwise helpers of the ring driver (HBM-bound). */
 /* dst_bf16[n] = (bf16) src_f32[n] */
 int lwm_cast_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream);
@@ -921,8 +1010,8 @@ int lwm_version(void);
 /* sizeof(LwmAttnArgs) (which = 0) / sizeof(LwmConvArgs) (1) / sizeof(LwmRingArgs) (2) / sizeof(LwmGemvArgs) (3) /
  * sizeof(LwmSampleArgs) (4) / sizeof(LwmKv8DecodeArgs) (5) / sizeof(LwmKv8PrefillArgs) (6) / sizeof(LwmAdamWArgs) (7) as
  * sizeof(LwmAdamWTensor) (8: an element of a device table that the caller lays out) / sizeof(LwmGemvW8Args) (9) /
- * sizeof(LwmKv4DecodeArgs) (10) / sizeof(LwmGemvW4Args) (11) / sizeof(LwmFramesArgs) (12) as
- * compiled into the library:
+ * sizeof(LwmKv4DecodeArgs) (10) / sizeof(LwmGemvW4Args) (11) / sizeof(LwmFramesArgs) (12) /
+ * sizeof(LwmKv6DecodeArgs) (13) / sizeof(LwmKv6PrefillArgs) (14) as compiled into the library:
  * lets a foreign-language binding verify its struct mirror at load time. */
 int lwm_sizeof(int which);
 

@@ -139,6 +139,16 @@ class LwmKv8PrefillArgs(C.Structure):
     ]
 
 
+class LwmKv6DecodeArgs(C.Structure):
+    """the field list of LwmKv4DecodeArgs: e8m0 scale bytes, strides in bytes; the cache rows are 96-byte heads of e2m3 blocks"""
+    _fields_ = list(LwmKv8DecodeArgs._fields_)
+
+
+class LwmKv6PrefillArgs(C.Structure):
+    """the field list of LwmKv8PrefillArgs; the scales are e8m0 bytes and their strides are in bytes"""
+    _fields_ = list(LwmKv8PrefillArgs._fields_)
+
+
 class LwmSampleArgs(C.Structure):
     _fields_ = [
         ("logits", C.c_void_p), ("ld", C.c_int64), ("rows", C.c_int32), ("V", C.c_int32),
@@ -255,6 +265,13 @@ PROTOTYPES = {
                                          C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
                                          C.c_void_p]),
     "lwm_attn_decode_kv4": (C.c_int, [C.POINTER(LwmKv4DecodeArgs), C.c_void_p]),
+    "lwm_kv6_cache_write": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
+                                     C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
+    "lwm_kv6_cache_write_at": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                         C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
+                                         C.c_void_p]),
+    "lwm_attn_decode_kv6": (C.c_int, [C.POINTER(LwmKv6DecodeArgs), C.c_void_p]),
+    "lwm_attn_prefill_kv6": (C.c_int, [C.POINTER(LwmKv6PrefillArgs), C.c_void_p]),
     "lwm_rope_bf16": (C.c_int, [LwmTensor4, LwmTensor4, C.c_void_p, C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p]),
     "lwm_rmsnorm_fwd_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
                                       C.c_float, C.c_void_p]),
@@ -315,7 +332,8 @@ def bind(lib):
         fn.argtypes = args
     for which, cls in ((0, LwmAttnArgs), (1, LwmConvArgs), (2, LwmRingArgs), (4, LwmSampleArgs), (5, LwmKv8DecodeArgs),
                        (6, LwmKv8PrefillArgs), (7, LwmAdamWArgs), (8, LwmAdamWTensor), (9, LwmGemvW8Args),
-                       (10, LwmKv4DecodeArgs), (11, LwmGemvW4Args), (12, LwmFramesArgs)):
+                       (10, LwmKv4DecodeArgs), (11, LwmGemvW4Args), (12, LwmFramesArgs), (13, LwmKv6DecodeArgs),
+                       (14, LwmKv6PrefillArgs)):
         if lib.lwm_sizeof(which) != C.sizeof(cls):
             raise ImportError(f"{cls.__name__}: ctypes mirror is {C.sizeof(cls)} bytes, library has "
                               f"{lib.lwm_sizeof(which)} (include/lwm_hip.h and lwm_amd/_capi.py out of step)")

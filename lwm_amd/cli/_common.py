@@ -42,15 +42,16 @@ def sampler_kwargs(model, seed, generator):
     decode kernels) -- and the same --seed gives the same tokens run after run.
     LWM_KV_CACHE=fp8: the 8-bit KV cache (generate(kv_dtype="fp8"): half the cache bytes, held and read per token;
     bf16 models on one rank), with either sampler.  LWM_KV_CACHE=fp4: the 4-bit MXFP4 KV cache (generate(kv_dtype="fp4"):
-    0.27 of the cache bytes; the same conditions, and no LWM_PREFILL_CHUNK with it).
+    0.27 of the cache bytes; the same conditions, and no LWM_PREFILL_CHUNK with it).  LWM_KV_CACHE=fp6: the 6-bit MXFP6 KV
+    cache (generate(kv_dtype="fp6"): 0.39 of the cache bytes; the 8-bit cache's conditions, LWM_PREFILL_CHUNK included).
     LWM_PREFILL_CHUNK=N: the prompt goes through the layers in blocks of N tokens (generate(prefill_chunk=N): the
-    prefill's activations are bounded by N; with the 8-bit cache every block after the first attends over quantised rows).
+    prefill's activations are bounded by N; with the 8-bit or the 6-bit cache every block after the first attends over quantised rows).
     LWM_TOP_P=p, 0 < p <= 1: nucleus sampling after temperature and top-k (generate(top_p=p)), with either sampler; the
     reference's flag set has no top_p, so it is an environment variable.  Unset or empty: nothing changes."""
     kv =os.environ.get("LWM_KV_CACHE", "").lower()
-    if kv not in ("", "bf16", "fp8", "fp4"):
-        raise SystemExit(f"LWM_KV_CACHE={kv!r}: 'fp4', 'fp8', 'bf16' (the default) or unset")
-    extra = dict(kv_dtype=kv) if kv in ("fp8", "fp4") else {}
+    if kv not in ("", "bf16", "fp8", "fp6", "fp4"):
+        raise SystemExit(f"LWM_KV_CACHE={kv!r}: 'fp6', 'fp4', 'fp8', 'bf16' (the default) or unset")
+    extra = dict(kv_dtype=kv) if kv in ("fp8", "fp6", "fp4") else {}
     chunk = os.environ.get("LWM_PREFILL_CHUNK", "")
     if chunk:
         try:

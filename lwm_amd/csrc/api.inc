@@ -9,6 +9,8 @@
 #include "attn_decode_kv8.h"
 #include "attn_decode_kv4.h"
 #include "attn_prefill_kv8.h"
+#include "attn_decode_kv6.h"
+#include "attn_prefill_kv6.h"
 #include "gemv_w8.h"
 #include "gemv_w4.h"
 #include "gemm_rows.h"
@@ -100,7 +102,7 @@ static AttnParams to_params(const LwmAttnArgs* a) {
     return p;
 }
 
-// The entries of the two quantised caches (attn_decode_kv8.h, attn_decode_kv4.h) share their checks.  What differs per
+// The entries of the quantised caches (attn_decode_kv8.h, attn_decode_kv4.h, attn_decode_kv6.h) share their checks.  What differs per
 // entry is passed in: the names, the kernel, the code that its shape and alignment refusals return, and the alignment
 // rule.  `at`: the destination row comes from device memory (row0_dev) and dst_row0 is the offset added to it.
 template <class P>
@@ -135,9 +137,10 @@ static int kvq_cache_write(const char* name, const char* kname, void (*kernel)(P
 }
 
 // head_bytes > 0: the strides are checked too (non-negative, a head no smaller than that).  scales_f32: the scale
-// pointers are checked for 4-byte alignment with lse_acc.
+// pointers are checked for 4-byte alignment with lse_acc.  row_align: 16, or 8 where a lane's part of a row is loaded in
+// 8-byte words.
 template <class F, class P, class Args>
-static int kvq_attn_decode(const char* name, void (*kernel)(P), int ecode, int head_bytes, bool scales_f32,
+static int kvq_attn_decode(const char* name, void (*kernel)(P), int ecode, int head_bytes, bool scales_f32, int row_align,
                            const Args* a, void* stream) {
     if (!a) return fail(LWM_EINVAL, "%s: args is null", name);
     int r;
@@ -147,9 +150,11 @@ static int kvq_attn_decode(const char* name, void (*kernel)(P), int ecode, int h
     if (!(a->scale > 0.0f)) return fail(LWM_EINVAL, "%s: scale must be > 0", name);
     if (!a->k || !a->v || !a->k_scale || !a->v_scale || !a->out_acc || !a->lse_acc)
         return fail(LWM_EINVAL, "%s: null pointer (k, v, k_scale, v_scale, out_acc, lse_acc)", name);
-    if (!aligned16(a->k) || !aligned16(a->v) || !aligned16(a->out_acc) || ((a->k_stride_b | a->k_stride_s | a->k_stride_h |
-                                                                          a->v_stride_b | a->v_stride_s | a->v_stride_h) & 15))
-        return fail(ecode, "%s: cache rows and out_acc must be 16-byte aligned (pointers and strides)", name);
+    if (!aligned16(a->out_acc) || (((uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->k_stride_b | (uintptr_t)a->k_stride_s |
+                                    (uintptr_t)a->k_stride_h | (uintptr_t)a->v_stride_b | (uintptr_t)a->v_stride_s |
+                                    (uintptr_t)a->v_stride_h) & (uintptr_t)(row_align - 1)))
+        return fail(ecode, row_align == 16 ? "%s: cache rows and out_acc must be 16-byte aligned (pointers and strides)"
+                                           : "%s: cache rows must be 8-byte and out_acc 16-byte aligned (pointers and strides)", name);
     if (head_bytes > 0 &&
         (a->k_stride_s < 0 || a->v_stride_s < 0 || a->k_stride_h < head_bytes || a->v_stride_h < head_bytes || a->k_scale_stride_s < 0 ||
          a->v_scale_stride_s < 0 || a->k_scale_stride_b < 0 || a->v_scale_stride_b < 0 || a->k_stride_b < 0 || a->v_stride_b < 0))
@@ -280,6 +285,7 @@ int lwm_kv_cache_write_at(void* cache, const void* src, int32_t B, int64_t cache
 
 static const char kKv8WriteAlign[] = "cache and src rows 16-byte aligned, scale 4-byte";
 static const char kKv4WriteAlign[] = "src rows 16-byte aligned, cache and scale rows 4-byte";
+static const char kKv6WriteAlign[] = "src rows 16-byte aligned, cache rows 8-byte, scale rows 4-byte";
 
 int lwm_kv8_cache_write(void* cache, const void* src, int32_t B, int64_t cache_stride_b,
                         int64_t src_stride_b, int64_t dst_row0, int64_t src_row0, int64_t nrows,
@@ -316,11 +322,73 @@ int lwm_kv4_cache_write_at(void* cache, const void* src, int32_t B, int64_t cach
 }
 
 int lwm_attn_decode_kv8(const LwmKv8DecodeArgs* a, void* stream) {
-    return lwm::kvq_attn_decode<lwm::Kv8Format>("attn_decode_kv8", lwm::attn_decode_kv8_kernel, LWM_EUNSUPPORTED, 0, true, a, stream);
+    return lwm::kvq_attn_decode<lwm::Kv8Format>("attn_decode_kv8", lwm::attn_decode_kv8_kernel, LWM_EUNSUPPORTED, 0, true, 16, a, stream);
 }
 
 int lwm_attn_decode_kv4(const LwmKv4DecodeArgs* a, void* stream) {
-    return lwm::kvq_attn_decode<lwm::Kv4Format>("attn_decode_kv4", lwm::attn_decode_kv4_kernel, LWM_EINVAL, 64, false, a, stream);
+    return lwm::kvq_attn_decode<lwm::Kv4Format>("attn_decode_kv4", lwm::attn_decode_kv4_kernel, LWM_EINVAL, 64, false, 16, a, stream);
+}
+
+int lwm_kv6_cache_write(void* cache, const void* src, int32_t B, int64_t cache_stride_b,
+                        int64_t src_stride_b, int64_t dst_row0, int64_t src_row0, int64_t nrows,
+                        int32_t row_elems, void* scale, int64_t scale_stride_b, int32_t H, void* stream) {
+    return lwm::kvq_cache_write("kv6_cache_write", "kv6_quant_write", lwm::kv6_quant_write_kernel, false, LWM_EINVAL, 8, 4,
+                                           kKv6WriteAlign, cache, src, B, cache_stride_b, src_stride_b, nullptr, dst_row0, 0, src_row0,
+                                           nrows, row_elems, scale, scale_stride_b, H, stream);
+}
+
+int lwm_kv6_cache_write_at(void* cache, const void* src, int32_t B, int64_t cache_stride_b,
+                           int64_t src_stride_b, const int32_t* dst_row0_dev, int64_t row_offset,
+                           int64_t cache_rows, int64_t src_row0, int64_t nrows, int32_t row_elems,
+                           void* scale, int64_t scale_stride_b, int32_t H, void* stream) {
+    return lwm::kvq_cache_write("kv6_cache_write_at", "kv6_quant_write_at", lwm::kv6_quant_write_at_kernel, true, LWM_EINVAL, 8, 4,
+                                           kKv6WriteAlign, cache, src, B, cache_stride_b, src_stride_b, dst_row0_dev, row_offset,
+                                           cache_rows, src_row0, nrows, row_elems, scale, scale_stride_b, H, stream);
+}
+
+int lwm_attn_decode_kv6(const LwmKv6DecodeArgs* a, void* stream) {
+    return lwm::kvq_attn_decode<lwm::Kv6Format>("attn_decode_kv6", lwm::attn_decode_kv6_kernel, LWM_EINVAL, 96, false, 8, a, stream);
+}
+
+int lwm_attn_prefill_kv6(const LwmKv6PrefillArgs* a, void* stream) {
+    using namespace lwm;
+    if (!a) return fail(LWM_EINVAL, "%s", "attn_prefill_kv6: args is null");
+    int r;
+    if ((r = check_t4("q", a->q, true))) return r;
+    if (a->D != kHeadDim) return fail(LWM_EUNSUPPORTED, "%s: head_dim %ld (only 128)", "attn_prefill_kv6", a->D);
+    if (a->B < 0 || a->Sq < 1 || a->Sk < 1 || a->H <= 0 || a->q_start < 0)
+        return fail(LWM_EINVAL, "%s", "attn_prefill_kv6: bad dimension (B >= 0, Sq >= 1, Sk >= 1, H >= 1, q_start >= 0)");
+    if (!(a->scale > 0.0f)) return fail(LWM_EINVAL, "%s", "attn_prefill_kv6: scale must be > 0");
+    if (!a->k || !a->v || !a->k_scale || !a->v_scale || !a->out_acc || !a->lse_acc)
+        return fail(LWM_EINVAL, "%s", "attn_prefill_kv6: null pointer (k, v, k_scale, v_scale, out_acc, lse_acc)");
+    if (!aligned16(a->out_acc) || (((uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->k_stride_b | (uintptr_t)a->k_stride_s |
+                                    (uintptr_t)a->k_stride_h | (uintptr_t)a->v_stride_b | (uintptr_t)a->v_stride_s |
+                                    (uintptr_t)a->v_stride_h) & 7))
+        return fail(LWM_EUNSUPPORTED, "%s", "attn_prefill_kv6: cache rows must be 8-byte and out_acc 16-byte aligned (pointers and strides)");
+    if (a->k_stride_s < 0 || a->v_stride_s < 0 || a->k_stride_h < 96 || a->v_stride_h < 96 || a->k_scale_stride_s < 0 ||
+        a->v_scale_stride_s < 0 || a->k_scale_stride_b < 0 || a->v_scale_stride_b < 0 || a->k_stride_b < 0 || a->v_stride_b < 0)
+        return fail(LWM_EINVAL, "%s", "attn_prefill_kv6: bad strides (non-negative; a head is 96 bytes)");
+    if (((uintptr_t)a->lse_acc) & 3) return fail(LWM_EUNSUPPORTED, "%s", "attn_prefill_kv6: lse_acc must be 4-byte aligned");
+    if (a->k_splits < 0 || a->k_splits > 4096) return fail(LWM_EINVAL, "%s", "attn_prefill_kv6: k_splits out of range");
+    if (a->B == 0) return LWM_OK;
+    Kv6PrefillParams p;
+    memset(&p, 0, sizeof(p));
+    p.a.q = (const bf16_t*)a->q.ptr; p.a.q_sb = a->q.stride_b; p.a.q_ss = a->q.stride_s; p.a.q_sh = a->q.stride_h;
+    p.a.out_acc = a->out_acc; p.a.lse_acc = a->lse_acc; p.a.key_valid = a->key_valid;
+    p.a.B = a->B; p.a.H = a->H; p.a.Sq = a->Sq; p.a.Sk = a->Sk;
+    p.a.q_start = a->q_start; p.a.k_start = 0; p.a.q_np = 1; p.a.k_np = 1;
+    p.a.scale = a->scale; p.a.causal = 1; p.a.carry_in = 0; p.a.final_out = 0;
+    p.a.k_splits = a->k_splits > 1 ? a->k_splits : 1;
+    p.k6 = (const uint8_t*)a->k; p.v6 = (const uint8_t*)a->v;
+    p.k_scale = (const uint8_t*)a->k_scale; p.v_scale = (const uint8_t*)a->v_scale;
+    p.k6_sb = a->k_stride_b; p.k6_ss = a->k_stride_s; p.k6_sh = a->k_stride_h;
+    p.v6_sb = a->v_stride_b; p.v6_ss = a->v_stride_s; p.v6_sh = a->v_stride_h;
+    p.ks_sb = a->k_scale_stride_b; p.ks_ss = a->k_scale_stride_s;
+    p.vs_sb = a->v_scale_stride_b; p.vs_ss = a->v_scale_stride_s;
+    p.kv_sb = a->key_valid_stride_b;
+    const long nqt = (p.a.Sq + kFwdBQ - 1) / kFwdBQ;
+    return launch("attn_prefill_kv6", attn_prefill_kv6_kernel, nqt * p.a.H * p.a.B * p.a.k_splits, kFwdThreads, kFwdLdsBytes,
+                  stream, p);
 }
 
 int lwm_attn_prefill_kv8(const LwmKv8PrefillArgs* a, void* stream) {
@@ -998,9 +1066,9 @@ int lwm_adamw_step(const LwmAdamWArgs* a, void* stream) {
 int lwm_adamw_chunk(void) { return lwm::kAdamWChunk; }
 
 const char* lwm_last_error(void) { return lwm::g_err; }
-int lwm_version(void) { return 620; }
+int lwm_version(void) { return 630; }
 int lwm_sizeof(int which) {
-    return which == 0 ? (int)sizeof(LwmAttnArgs) : which == 1 ? (int)sizeof(LwmConvArgs) : which == 2 ? (int)sizeof(LwmRingArgs) : which == 3 ? (int)sizeof(LwmGemvArgs) : which == 4 ? (int)sizeof(LwmSampleArgs) : which == 5 ? (int)sizeof(LwmKv8DecodeArgs) : which == 6 ? (int)sizeof(LwmKv8PrefillArgs) : which == 7 ? (int)sizeof(LwmAdamWArgs) : which == 8 ? (int)sizeof(LwmAdamWTensor) : which == 9 ? (int)sizeof(LwmGemvW8Args) : which == 10 ? (int)sizeof(LwmKv4DecodeArgs) : which == 11 ? (int)sizeof(LwmGemvW4Args) : which == 12 ? (int)sizeof(LwmFramesArgs) : -1;
+    return which == 0 ? (int)sizeof(LwmAttnArgs) : which == 1 ? (int)sizeof(LwmConvArgs) : which == 2 ? (int)sizeof(LwmRingArgs) : which == 3 ? (int)sizeof(LwmGemvArgs) : which == 4 ? (int)sizeof(LwmSampleArgs) : which == 5 ? (int)sizeof(LwmKv8DecodeArgs) : which == 6 ? (int)sizeof(LwmKv8PrefillArgs) : which == 7 ? (int)sizeof(LwmAdamWArgs) : which == 8 ? (int)sizeof(LwmAdamWTensor) : which == 9 ? (int)sizeof(LwmGemvW8Args) : which == 10 ? (int)sizeof(LwmKv4DecodeArgs) : which == 11 ? (int)sizeof(LwmGemvW4Args) : which == 12 ? (int)sizeof(LwmFramesArgs) : which == 13 ? (int)sizeof(LwmKv6DecodeArgs) : which == 14 ? (int)sizeof(LwmKv6PrefillArgs) : -1;
 }
 
 }  // extern "C"

@@ -72,15 +72,20 @@ struct Kv4Format {
         for (int j = 0; j < 8; ++j) w |= f32_to_e2m1(y[j]) << (4 * j);
         return w;
     }
-    static constexpr int kLanes = 4;
+    LWM_FORMAT_FN void store(uint8_t* head, int li, uint32_t w, bool ok) { store_lane_codes<Kv4Format>(head, li, w, ok); }
+    static constexpr int kLanes = 4, kLaneDwords = 4;
+    typedef u32x4 codes_t;
+    LWM_FORMAT_FN u32x4 load_lane(const uint8_t* p) { return global_load_b128(p); }
     LWM_FORMAT_FN int scale_index(int h, int li) { return h * 4 + li; }
     LWM_FORMAT_FN uint32_t load_scale(const uint8_t* p) { return global_load_u8(p); }
     LWM_FORMAT_FN float scale_f32(uint32_t bits) { return e8m0_to_f32(bits); }
-    LWM_FORMAT_FN void cvt_dword(uint32_t w, f32x2 (&f)[4]) {
-        f[0] = cvt_e2m1x2<0>(w);
-        f[1] = cvt_e2m1x2<1>(w);
-        f[2] = cvt_e2m1x2<2>(w);
-        f[3] = cvt_e2m1x2<3>(w);
+    LWM_FORMAT_FN void cvt_lane(u32x4 w, f32x2 (&f)[16]) {
+        for (int i = 0; i < 4; ++i) {
+            f[4 * i] = cvt_e2m1x2<0>(w[i]);
+            f[4 * i + 1] = cvt_e2m1x2<1>(w[i]);
+            f[4 * i + 2] = cvt_e2m1x2<2>(w[i]);
+            f[4 * i + 3] = cvt_e2m1x2<3>(w[i]);
+        }
     }
     LWM_FORMAT_FN float scale_lane(float a, float ks) { return a * ks; }
     LWM_FORMAT_FN float scale_head(float a, float) { return a; }

@@ -83,13 +83,18 @@ struct Kv8Format {
     LWM_FORMAT_FN u32x2 encode(const float (&y)[8]) {
         return u32x2{pack_e4m3x4(y[0], y[1], y[2], y[3]), pack_e4m3x4(y[4], y[5], y[6], y[7])};
     }
-    static constexpr int kLanes = 8;
+    LWM_FORMAT_FN void store(uint8_t* head, int li, u32x2 w, bool ok) { store_lane_codes<Kv8Format>(head, li, w, ok); }
+    static constexpr int kLanes = 8, kLaneDwords = 4;
+    typedef u32x4 codes_t;
+    LWM_FORMAT_FN u32x4 load_lane(const uint8_t* p) { return global_load_b128(p); }
     LWM_FORMAT_FN int scale_index(int h, int) { return h; }
     LWM_FORMAT_FN uint32_t load_scale(const float* p) { return __builtin_bit_cast(uint32_t, global_load_f32(p)); }
     LWM_FORMAT_FN float scale_f32(uint32_t bits) { return __builtin_bit_cast(float, bits); }
-    LWM_FORMAT_FN void cvt_dword(uint32_t w, f32x2 (&f)[2]) {
-        f[0] = cvt_e4m3x2_lo(w);
-        f[1] = cvt_e4m3x2_hi(w);
+    LWM_FORMAT_FN void cvt_lane(u32x4 w, f32x2 (&f)[8]) {
+        for (int i = 0; i < 4; ++i) {
+            f[2 * i] = cvt_e4m3x2_lo(w[i]);
+            f[2 * i + 1] = cvt_e4m3x2_hi(w[i]);
+        }
     }
     LWM_FORMAT_FN float scale_lane(float a, float) { return a; }
     LWM_FORMAT_FN float scale_head(float a, float ks) { return a * ks; }

@@ -1,8 +1,8 @@
 // attn_decode_kvq.h -- what the quantised KV caches share: the quantising cache write and the cached-decode attention
 // kernel, written once over a compile-time description of the format.  Requires wave_ops.h + attn_common.h +
 // attn_decode.h (unpack_bf16x8, decode_visible_range, f32x2, fma2, issue_fence, the scalar loads and stores).  The
-// formats -- their layout, codec and description struct, and the __global__ entry points -- are attn_decode_kv8.h and
-// attn_decode_kv4.h.
+// formats -- their layout, codec and description struct, and the __global__ entry points -- are attn_decode_kv8.h,
+// attn_decode_kv4.h and attn_decode_kv6.h.
 //
 // A format description F has only static members:
 //   scale_t                         element type of the scale tensors
@@ -11,11 +11,15 @@
 //          kExpDrop, kMantTop       amax = 1.m * 2^e gets the scale 2^(e - kExpDrop), one more where the 7 bits of m > kMantTop
 //          scale_of(se)             the biased exponent of the scale -> the stored scale_t
 //          encode(y)                the lane's 8 scaled values -> their codes, one or two dwords
-//   decode: kLanes                  lanes that own a head (16 bytes of each row per lane: 128 / kLanes elements)
+//          store(head, li, w, ok)   the lane's codes -> their bytes of the head row at `head`, where ok (every lane of the
+//                                   wave calls it: a format may shuffle)
+//   decode: kLanes                  lanes that own a head (128 / kLanes elements and kLaneDwords dwords of each row per lane)
+//           kLaneDwords, codes_t    the lane's dwords of one row, and the vector of them
+//           load_lane(ptr)          the lane's codes of one row (naturally aligned loads)
 //           scale_index(h, li)      index of the lane's scale among the scales of one row
 //           load_scale(ptr)         the scale's bits; zero bits stand for a masked key
 //           scale_f32(bits)         (cleared) bits -> f32
-//           cvt_dword(w, f)         one dword of codes -> 128 / kLanes / 8 f32 pairs, element order
+//           cvt_lane(w, f)          the lane's codes -> its 128 / kLanes / 2 f32 pairs, element order
 //           scale_lane(a, ks)       the lane's partial score before the reduction over the lanes of the head ...
 //           scale_head(a, ks)       ... and the head's score after it: one of the two multiplies by ks
 #pragma once
@@ -49,6 +53,11 @@ struct KvqWriteParams {
 // workgroup; what a lane may not do is decided at the loads and stores).
 LWM_DEVICE void store_codes(uint8_t* p, uint32_t w) { global_store_b32(p, w); }
 LWM_DEVICE void store_codes(uint8_t* p, u32x2 w) { global_store_b64(p, w); }
+// F::store of a format whose lane's 8 codes are one naturally aligned unit: kHeadBytes / 16 bytes at li * that
+template <class F, class W>
+LWM_DEVICE void store_lane_codes(uint8_t* head, int li, W w, bool ok) {
+    if (ok) store_codes(head + li * (F::kHeadBytes / 16), w);
+}
 
 template <class F>
 LWM_DEVICE void kv_quant_rows(const KvqWriteParams<F>& p, int64_t dst_row0) {
@@ -87,11 +96,10 @@ LWM_DEVICE void kv_quant_rows(const KvqWriteParams<F>& p, int64_t dst_row0) {
         for (int j = 0; j < 8; ++j) x[j] *= inv;
         const auto w = F::encode(x);
         const typename F::scale_t s = F::scale_of(se);
-        if (in && dr >= 0 && dr < p.cache_rows) {
-            store_codes(p.cache + b * p.cache_sb + (dr * p.H + h) * F::kHeadBytes + li * (F::kHeadBytes / 16), w);
-            if ((li & (F::kAmaxLanes - 1)) == 0)
-                p.scale[b * p.scale_sb + (dr * p.H + h) * (16 / F::kAmaxLanes) + li / F::kAmaxLanes] = s;
-        }
+        const bool ok = in && dr >= 0 && dr < p.cache_rows;
+        F::store(p.cache + b * p.cache_sb + (dr * p.H + h) * F::kHeadBytes, li, w, ok);
+        if (ok && (li & (F::kAmaxLanes - 1)) == 0)
+            p.scale[b * p.scale_sb + (dr * p.H + h) * (16 / F::kAmaxLanes) + li / F::kAmaxLanes] = s;
     }
 }
 
@@ -123,22 +131,24 @@ constexpr int kDecqLdsBytes = (kDecqSlots<F> / 2) * (kHeadDim + 2) * 4;     // t
 
 // The same contract as attn_decode_kernel -- one workgroup per (batch row, piece of the VISIBLE key range), holes
 // handled per key, per-piece phase rotation, normalised partials merged by attn_combine_kernel, nothing visible =
-// (0, -inf) -- over smaller rows.  kLanes lanes x 16 B own a head row (lane i holds the 128 / kLanes elements from
-// i * 128 / kLanes on of q, of the running output and of each K/V row) and the workgroup has 512 / kLanes head slots.
+// (0, -inf) -- over smaller rows.  kLanes lanes x kLaneDwords dwords own a head row (lane i holds the 128 / kLanes elements
+// from i * 128 / kLanes on of q, of the running output and of each K/V row) and the workgroup has 512 / kLanes head slots.
 // Where H is smaller the slots beyond the first HS = H rounded up to a power of two take further KEYS:
 // slot = kl * HS + head, the workgroup walks KP = slots / HS keys per pass (a wave load is still 1 KiB contiguous), each
 // key lane kl keeps its own online-softmax state over the keys = kl (mod KP) of the piece.  The KP states of a head are
 // merged through LDS by halving: the upper half of the key lanes leaves (o, m, l), the lower half folds it in, until
-// key lane 0 holds the piece -- a fixed order.  Keys are taken kDecUnroll passes at a time: 8 x 16-byte row loads in
-// flight per lane as in the bf16 kernel.  The scales of a (key, head) are loaded WITH its rows -- their addresses depend
+// key lane 0 holds the piece -- a fixed order.  Keys are taken kDecUnroll passes at a time: 8 row loads of a lane's
+// width in flight per lane (16 bytes each as in the bf16 kernel, or 24 as three 8-byte loads).  The scales of a (key, head) are loaded WITH its rows -- their addresses depend
 // on nothing the rows bring -- and p_v = p * value_scale.  A masked key contributes exactly nothing whatever its bytes
 // and scales hold (NaN patterns, NaN scales): its score is -inf by selection and its rows and scale bits are cleared by
 // bit masks before they are converted.
 template <class F>
 LWM_DEVICE void attn_decode_kvq(const KvqDecodeParams<F>& p) {
     constexpr int L = F::kLanes, S = kDecqSlots<F>;
-    constexpr int E = kHeadDim / L;                    // elements of a head per lane: E / 8 f32 pairs per dword of codes,
-    constexpr int NP = E / 2;                          // NP pairs of q and of o
+    constexpr int E = kHeadDim / L;                    // elements of a head per lane,
+    constexpr int NP = E / 2;                          // NP pairs of q, of o and of a converted row
+    constexpr int W = F::kLaneDwords;
+    typedef typename F::codes_t codes_t;
     const int tid = thread_idx();
     const int slot = (int)((uint32_t)tid / L), li = (int)((uint32_t)tid % L);
     const int nsplit = p.k_splits > 1 ? p.k_splits : 1;
@@ -172,8 +182,8 @@ LWM_DEVICE void attn_decode_kvq(const KvqDecodeParams<F>& p) {
             for (int j = 0; j < NP; ++j) o[j] = f32x2{0.0f, 0.0f};
         }
         float m = -INFINITY, l = 0.0f;
-        const uint8_t* kb = p.k + (int64_t)b * p.k_sb + (int64_t)hc * p.k_sh + li * 16;
-        const uint8_t* vb = p.v + (int64_t)b * p.v_sb + (int64_t)hc * p.v_sh + li * 16;
+        const uint8_t* kb = p.k + (int64_t)b * p.k_sb + (int64_t)hc * p.k_sh + li * (W * 4);
+        const uint8_t* vb = p.v + (int64_t)b * p.v_sb + (int64_t)hc * p.v_sh + li * (W * 4);
         const typename F::scale_t* ksb = p.k_scale + (int64_t)b * p.ks_sb + F::scale_index(hc, li);
         const typename F::scale_t* vsb = p.v_scale + (int64_t)b * p.vs_sb + F::scale_index(hc, li);
         // every piece starts at a different phase of its key range (see attn_decode.h)
@@ -182,7 +192,7 @@ LWM_DEVICE void attn_decode_kvq(const KvqDecodeParams<F>& p) {
         for (int g = 0; g < nq; ++g) {
             const int gq = g + rot < nq ? g + rot : g + rot - nq;
             const int j0 = ka + gq * span + kl;
-            u32x4 kr[kDecUnroll], vr[kDecUnroll];
+            codes_t kr[kDecUnroll], vr[kDecUnroll];
             uint32_t ksw[kDecUnroll], vsw[kDecUnroll];
             uint8_t mb[kDecUnroll];
             bool vis[kDecUnroll];
@@ -194,8 +204,8 @@ LWM_DEVICE void attn_decode_kvq(const KvqDecodeParams<F>& p) {
                 const int jj = j0 + u * KP;
                 const int j = jj < kz ? jj : kz - 1;                 // clamped: loads stay in bounds
                 const uint8_t* kp = kb + (int64_t)j * p.k_ss;
-                kr[u] = global_load_b128(kp);
-                vr[u] = global_load_b128(vb + (int64_t)j * p.v_ss);
+                kr[u] = F::load_lane(kp);
+                vr[u] = F::load_lane(vb + (int64_t)j * p.v_ss);
                 ksw[u] = F::load_scale(ksb + (int64_t)j * p.ks_ss);
                 vsw[u] = F::load_scale(vsb + (int64_t)j * p.vs_ss);
                 mb[u] = global_load_u8(mrow ? mrow + j : kp);
@@ -207,7 +217,7 @@ LWM_DEVICE void attn_decode_kvq(const KvqDecodeParams<F>& p) {
             for (int u = 0; u < kDecUnroll; ++u) {
                 vis[u] = (j0 + u * KP < kz) & (!mrow | (mb[u] != 0));
                 const uint32_t keep = 0u - (uint32_t)vis[u];
-                for (int w = 0; w < 4; ++w) {
+                for (int w = 0; w < W; ++w) {
                     kr[u][w] &= keep;
                     vr[u][w] &= keep;
                 }
@@ -218,11 +228,9 @@ LWM_DEVICE void attn_decode_kvq(const KvqDecodeParams<F>& p) {
             float mx = -INFINITY;
             for (int u = 0; u < kDecUnroll; ++u) {
                 f32x2 a2 = {0.0f, 0.0f};
-                for (int w = 0; w < 4; ++w) {
-                    f32x2 kf[E / 8];
-                    F::cvt_dword(kr[u][w], kf);
-                    for (int j = 0; j < E / 8; ++j) a2 = fma2(qf[E / 8 * w + j], kf[j], a2);
-                }
+                f32x2 kf[NP];
+                F::cvt_lane(kr[u], kf);
+                for (int j = 0; j < NP; ++j) a2 = fma2(qf[j], kf[j], a2);
                 float a = F::scale_lane(a2[0] + a2[1], ks[u]);
 #pragma unroll
                 for (int msk = 1; msk < L; msk <<= 1) a += shfl_xor_f(a, msk);
@@ -239,11 +247,9 @@ LWM_DEVICE void attn_decode_kvq(const KvqDecodeParams<F>& p) {
                 l += pu;
                 const float pv = pu * vs[u];
                 const f32x2 pv2 = {pv, pv};
-                for (int w = 0; w < 4; ++w) {
-                    f32x2 vf[E / 8];
-                    F::cvt_dword(vr[u][w], vf);
-                    for (int j = 0; j < E / 8; ++j) o[E / 8 * w + j] = fma2(pv2, vf[j], o[E / 8 * w + j]);
-                }
+                f32x2 vf[NP];
+                F::cvt_lane(vr[u], vf);
+                for (int j = 0; j < NP; ++j) o[j] = fma2(pv2, vf[j], o[j]);
             }
             m = m_new;
         }

@@ -16,7 +16,7 @@ import os
 
 import torch
 
-from . import kv4 as _kv4, ops as _ops
+from . import kv4 as _kv4, kv6 as _kv6, ops as _ops
 from .llama_ops import (LLaMAMLP, RMSNorm, apply_rotary_emb, chunked_lm_head_loss, decode_rows_scope, dense, dense_fused,
                         dense_multi, fused_dense_ok, parse_decode_rows, precompute_freqs_cis, qkv_rope, rmsnorm_residual,
                         rows_x_ok, swiglu)
@@ -242,7 +242,9 @@ class LLaMAAttention(torch.nn.Module):
         if "key_scale" in cache:
             return self._cached_kvq(_ops.KV8, xq, xk, xv, attention_mask, cache)
         if "key_scale_e8m0" in cache:
-            return self._cached_kvq(_kv4.KV4, xq, xk, xv, attention_mask, cache)
+            # the 4-bit and the 6-bit cache name their scale tensors alike: a head of cached_key is 64 or 96 bytes
+            f = _kv6.KV6 if ck.shape[-1] == _kv6.KV6.head_bytes else _kv4.KV4
+            return self._cached_kvq(f, xq, xk, xv, attention_mask, cache)
         if "index_dev" in cache:
             # hipGraph-capturable decode step: cache_index lives on the device (one int32 shared by all
             # layers), the mask was built from it once for this step, and the new row is written by
@@ -273,11 +275,11 @@ class LLaMAAttention(torch.nn.Module):
         return ringattention_inference(xq.contiguous(), ck, cv, mask, axis_name="sp")
 
     def _cached_kvq(self, f, xq, xk, xv, attention_mask, cache):
-        """_cached over a quantised cache of format f (init_cache(kv_dtype="fp8" / "fp4"): ops.KV8, kv4.KV4;
-        csrc/attn_decode_kv8.h, attn_decode_kv4.h).  Prefill (cache_index == 0): the cached path attends over rows [0, Q)
+        """_cached over a quantised cache of format f (init_cache(kv_dtype="fp8" / "fp6" / "fp4"): ops.KV8, kv6.KV6, kv4.KV4;
+        csrc/attn_decode_kv8.h, attn_decode_kv6.h, attn_decode_kv4.h).  Prefill (cache_index == 0): the cached path attends over rows [0, Q)
         only -- rows past Q are invisible -- so the block attends over its OWN bf16 keys and values under the same
         structured mask, and the rows are quantised into the cache afterwards: the prompt's own attention sees
-        unquantised keys.  A decode step quantises its row, then streams the cache (lwm_attn_decode_kv8 / _kv4 + the
+        unquantised keys.  A decode step quantises its row, then streams the cache (lwm_attn_decode_kv8 / _kv6 / _kv4 + the
         split-K combine).  A block at cache_index > 0 is refused unless the format has a block kernel and the cache was
         made for blocks."""
         from .ring import _pick_splits
@@ -311,10 +313,10 @@ class LLaMAAttention(torch.nn.Module):
             if Q != 1:
                 # a block appended to a live cache (init_cache(chunked_prefill=True)): the decode step's rule -- quantise
                 # your own rows, then read the cache -- for Q rows at once: the same as feeding the tokens one at a time.
-                # lwm_attn_prefill_kv8 dequantises while it stages; no bf16 copy of the cache is made
-                from .kv8 import attn_prefill_kv8
+                # the format's block kernel (lwm_attn_prefill_kv8 / _kv6) dequantises while it stages; no bf16 copy of the
+                # cache is made
                 kvld = None if attention_mask is None else (attention_mask[:, :n] != 0).to(torch.uint8)
-                o_parts, l_parts = attn_prefill_kv8(xq, ck[:, :n], ks[:, :n], cv[:, :n], vs[:, :n], q_start=idx,
+                o_parts, l_parts = _ops._kvq_block_fn(f)(xq, ck[:, :n], ks[:, :n], cv[:, :n], vs[:, :n], q_start=idx,
                                                     k_splits=_pick_splits(B, Q, H, n), key_valid=kvld)
                 if o_parts.shape[0] == 1:
                     # one piece: the partial IS the normalised output, and attn_combine's merge of one piece is the
@@ -578,21 +580,25 @@ class LLaMAForCausalLM(torch.nn.Module):
         kv_dtype="fp4" (extension): the 4-bit MXFP4 cache of csrc/attn_decode_kv4.h -- per layer cached_key / cached_value
         as uint8 (B, max_length, H, 64) e2m1 nibble pairs plus key_scale_e8m0 / value_scale_e8m0 (B, max_length, H, 4) e8m0
         bytes: 0.27 of the bytes.  bf16 models on one rank; a prompt at cache_index 0, then one token per step;
-        chunked_prefill=True is refused (a block kernel over the 4-bit cache is not built)."""
+        chunked_prefill=True is refused (a block kernel over the 4-bit cache is not built).
+        kv_dtype="fp6" (extension): the 6-bit MXFP6 cache of csrc/attn_decode_kv6.h -- per layer cached_key / cached_value
+        as uint8 (B, max_length, H, 96) e2m3 blocks plus key_scale_e8m0 / value_scale_e8m0 (B, max_length, H, 4) e8m0 bytes:
+        0.39 of the bytes.  bf16 models on one rank; takes chunked_prefill=True as the 8-bit cache does."""
         device = device or self.wte.device
         H = self.cfg.num_attention_heads
         D = self.cfg.hidden_size // H
         n_sp = sp_size_rank("sp")[0]
         if max_length % n_sp:
             raise ValueError(f"max_length {max_length} is not divisible by the sp ring size {n_sp}")
-        if kv_dtype not in (None, "fp8", "fp4"):
-            raise ValueError(f"kv_dtype={kv_dtype!r}: None (the model's dtype), 'fp8' or 'fp4'")
+        formats = {"fp8": _ops.KV8, "fp6": _kv6.KV6, "fp4": _kv4.KV4}
+        if kv_dtype is not None and kv_dtype not in formats:
+            raise ValueError(f"kv_dtype={kv_dtype!r}: None (the model's dtype), 'fp6', 'fp8' or 'fp4'")
         if kv_dtype is not None:
-            f = _ops.KV8 if kv_dtype == "fp8" else _kv4.KV4
+            f = formats[kv_dtype]
             _kvq_refuse(f, self.dtype, n_sp, D)
             if chunked_prefill and not f.block_kernel:
                 raise NotImplementedError(f"kv_dtype={f.kv_dtype!r} with chunked prefill (chunked_prefill=True, prefill_chunk=N): a "
-                                          f"block kernel over the {f.bits} cache is not built; kv_dtype='fp8' takes blocks")
+                                          f"block kernel over the {f.bits} cache is not built; kv_dtype='fp8' and 'fp6' take blocks")
             q = lambda: torch.zeros(batch_size, max_length, H, f.head_bytes, dtype=torch.uint8, device=device)
             sc = lambda: torch.full((batch_size, max_length, H) + f.scale_tail, f.scale_one, dtype=f.scale_dtype, device=device)
             mark = dict(kv8_blocks=True) if chunked_prefill else {}
@@ -623,10 +629,11 @@ class LLaMAForCausalLM(torch.nn.Module):
 
         kv_dtype="fp8": the 8-bit KV cache (init_cache); the prompt attends over its own bf16 keys, every later
         step over the quantised cache.  Works with graph=True.  kv_dtype="fp4": the 4-bit MXFP4 cache, by the same
-        rules; prefill_chunk is refused with it (a block kernel over the 4-bit cache is not built).
+        rules; prefill_chunk is refused with it (a block kernel over the 4-bit cache is not built).  kv_dtype="fp6": the
+        6-bit MXFP6 cache, by the 8-bit cache's rules, prefill_chunk included.
 
         prefill_chunk=N: the prompt goes through the layers in blocks of N tokens (the last may be shorter), so the
-        transient activations of the prefill are bounded by N instead of the prompt length.  With kv_dtype="fp8" the
+        transient activations of the prefill are bounded by N instead of the prompt length.  With kv_dtype="fp8" or "fp6" the
         cache is created with chunked_prefill=True: the first block sees its own unquantised keys, every later block the
         quantised rows (init_cache).  One rank; works with graph=True (the captured step starts after the prefill)."""
         B, S = input_ids.shape
@@ -782,7 +789,7 @@ def cache_kwargs(kv_dtype, prefill_chunk=None):
     """The keyword arguments of init_cache for a generate() call: only what is non-default is passed, so that a stand-in
     model with the three-argument init_cache keeps working."""
     kw = {} if kv_dtype is None else dict(kv_dtype=kv_dtype)
-    if kv_dtype in ("fp8", "fp4") and prefill_chunk is not None:
+    if kv_dtype in ("fp8", "fp6", "fp4") and prefill_chunk is not None:
         kw["chunked_prefill"] = True             # (init_cache refuses it for 'fp4', by name)
     return kw
 

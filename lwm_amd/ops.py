@@ -274,7 +274,7 @@ def kv_cache_write_at(cache, src, index_dev, *, row_offset=0, src_row0=0, nrows=
 
 class KvFormat(typing.NamedTuple):
     """What the front end knows of a quantised KV cache format (csrc/attn_decode_kvq.h; the formats themselves:
-    include/lwm_hip.h).  KV8 below, lwm_amd.kv4.KV4."""
+    include/lwm_hip.h).  KV8 below, lwm_amd.kv4.KV4, lwm_amd.kv6.KV6."""
     name: str                   # "kv8": the prefix of the public names and of the error messages
     kv_dtype: str               # "fp8": what init_cache / generate call it
     bits: str                   # "8-bit"
@@ -288,7 +288,18 @@ class KvFormat(typing.NamedTuple):
     write_at: str
     decode: str
     decode_args: type
-    block_kernel: bool          # a block of queries over the cache (lwm_amd.kv8.attn_prefill_kv8)?
+    block_kernel: bool          # a block of queries over the cache?
+    block: str = "lwm_amd.kv8:attn_prefill_kv8"      # ... then "module:function" of its front end (_kvq_block_fn below)
+
+
+def _kvq_block_fn(f):
+    """The front end of format f's block kernel: f(q, cached_key, key_scale, cached_value, value_scale, *, q_start,
+    k_splits, key_valid) -> partials.  Imported on use (the module of a format imports this one)."""
+    import importlib
+    if not f.block_kernel:
+        raise NotImplementedError(f"a block kernel over the {f.bits} cache is not built")
+    mod, name = f.block.split(":")
+    return getattr(importlib.import_module(mod), name)
 
 
 KV8 = KvFormat("kv8", "fp8", "8-bit", "e4m3 bytes", 128, torch.float32, (), 1.0, ("key_scale", "value_scale"),

@@ -241,7 +241,8 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
         include/lwm_hip.h (an entry stays iff the softmax mass strictly above it is below p); None or 1.0 = off, anything
         else a ValueError; greedy decoding ignores it.
         kv_dtype="fp8": the 8-bit KV cache (LLaMAModel.init_cache), on every one of these routes.  kv_dtype="fp4": the 4-bit
-        MXFP4 cache, likewise (no prefill_chunk with it: a block kernel over the 4-bit cache is not built).  prefill_chunk=N: the
+        MXFP4 cache, likewise (no prefill_chunk with it: a block kernel over the 4-bit cache is not built).  kv_dtype="fp6": the
+        6-bit MXFP6 cache, likewise, prefill_chunk included.  prefill_chunk=N: the
         prompt in blocks of N tokens (LLaMAForCausalLM.generate), on every one of these routes too."""
         top_p = _ops._check_top_p(top_p, "generate")
         if self.cfg.sample_mode != "text":
@@ -289,7 +290,7 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
 
         Sampling as generate(): generator= = the torch sampler, eager; seed= = ops.sample_tokens on the device, which
         also mixes the halves, forces the end-of-frame code and feeds both halves; seed= with graph=True = that step
-        captured once in a hipGraph and replayed (bf16, one rank).  kv_dtype="fp8" / "fp4": the 8-bit / 4-bit KV cache;
+        captured once in a hipGraph and replayed (bf16, one rank).  kv_dtype="fp8" / "fp6" / "fp4": the 8-bit / 6-bit / 4-bit KV cache;
         prefill_chunk=N: the prompt in blocks of N tokens (LLaMAForCausalLM.generate).  top_p as generate()."""
         top_p = _ops._check_top_p(top_p, "generate_vision")
         if self.cfg.sample_mode != "vision":
