@@ -19,7 +19,10 @@ job's: a debug model's 2 heads make 64 workgroups for 256 CUs, and the longest w
 lwm_amd.optim.FusedAdamW: the same --optimizer.adamw_optimizer.* values, weight decay on every parameter (the reference's
 get_weight_decay_exclusions() is empty, lwm/llama.py:286-287), f32 master weights and moments under bf16 parameters (the
 reference's param_dtype=float32), four HIP launches for clipping + update, and `gradient_norm` / `param_norm` in every
-record (lwm/train.py:216-222).  It runs on the gradients as they are after the all-reduce and adds no communication."""
+record (lwm/train.py:216-222).  It runs on the gradients as they are after the all-reduce and adds no communication.
+
+--lwm_remat_block (off by default) sets model.remat_blocks: per-block activation recompute (lwm_amd/remat.py), the same
+loss and gradients from about an eighth of the kept activations; LWM_REMAT_BLOCK=1 does the same without the flag."""
 from __future__ import annotations
 
 import math
@@ -36,7 +39,7 @@ DEFAULTS = dict(
     load_llama_config="", update_llama_config="", load_checkpoint="", load_dataset_state="", log_freq=50,
     save_model_freq=0, save_milestone_freq=0, eval_steps=0, tokenizer="LargeWorldModel/LWM-Text-1M",
     log_all_worker=False, autoresume=False, lwm_dump_grads="", lwm_balance_report=False, lwm_balance_seq=0, lwm_balance_heads=0,
-    lwm_fused_optimizer=False)
+    lwm_fused_optimizer=False, lwm_remat_block=False)
 GROUPS = ("train_dataset", "eval_dataset", "optimizer", "checkpointer", "llama", "logger", "jax_distributed")
 
 
@@ -70,6 +73,10 @@ def main(argv=None):
     cfg = C.build_config(F, vision)
     dtype = C.torch_dtype(F.dtype)
     model = C.load_checkpoint(C.build_model(cfg, vision, dtype, F.seed, dev), F.load_checkpoint)
+    if F.lwm_remat_block:
+        model.remat_blocks = True
+        C.note("activation recompute: every block keeps its input and the attention op's out / lse, and runs its other "
+               "operators again in the backward (lwm_amd/remat.py)")
     from ..llama_ops import use_tuned_gemms
     if use_tuned_gemms():
         C.note("library GEMMs: tuned solutions of lwm_amd/gemm_tuning_gfx950.csv where a shape is listed (LWM_GEMM_TUNING=0: off)")

@@ -16,7 +16,7 @@ import os
 
 import torch
 
-from . import kv4 as _kv4, kv6 as _kv6, ops as _ops
+from . import kv4 as _kv4, kv6 as _kv6, ops as _ops, remat as _remat
 from .llama_ops import (LLaMAMLP, RMSNorm, apply_rotary_emb, chunked_lm_head_loss, decode_rows_scope, dense, dense_fused,
                         dense_multi, fused_dense_ok, parse_decode_rows, precompute_freqs_cis, qkv_rope, rmsnorm_residual,
                         rows_x_ok, swiglu)
@@ -386,6 +386,7 @@ class LLaMAForCausalLM(torch.nn.Module):
         self._w8 = None            # quantize_decode_weights("fp8"): {parameter name: lwm_amd.w8.W8Kernel}
         self._w4 = None            # quantize_decode_weights("fp4"): {parameter name: lwm_amd.w4.W4Kernel}; _w8 stays None
         self._decode_rows = None   # decode_rows: None = LWM_DECODE_ROWS
+        self._remat_blocks = None  # remat_blocks: None = LWM_REMAT_BLOCK
 
     def _table(self, device):
         if self._freqs is None or self._freqs.device != device:
@@ -431,6 +432,20 @@ class LLaMAForCausalLM(torch.nn.Module):
     def decode_rows(self, n):
         self._decode_rows = parse_decode_rows(n, "decode_rows")
 
+    @property
+    def remat_blocks(self):
+        """Per-block activation recompute (lwm_amd/remat.py): a training step keeps, per block, its input and the
+        attention op's out / lse -- remat.saved_bytes -- and runs the block's other operators again in the backward; the
+        attention forward is not run again.  Same loss and gradients.  Opt-in; None (the default) reads LWM_REMAT_BLOCK
+        (1 = on; 0, "" or unset = off; anything else raises ValueError), True / False set it.  Inert with a KV cache,
+        under no_grad, where nothing requires a gradient and inside a hipGraph capture."""
+        rb = getattr(self, "_remat_blocks", None)
+        return _remat.parse_remat_block(os.environ.get(_remat.ENV)) if rb is None else rb
+
+    @remat_blocks.setter
+    def remat_blocks(self, on):
+        self._remat_blocks = None if on is None else _remat.parse_remat_block(on, "remat_blocks")
+
     def hidden_states(self, input_ids, attention_mask=None, segment_ids=None, position_ids=None, cache=None, layout=None):
         n_sp, position_ids = self._ring_position_ids(input_ids, position_ids, cache, layout)
         x = torch.nn.functional.embedding(input_ids.long(), self.wte)
@@ -442,9 +457,19 @@ class LLaMAForCausalLM(torch.nn.Module):
         if cache is not None and self._fused_decode_ok(x, n_sp):
             return self.ln_f(self._decode_layers_fused(x, fc, attention_mask, position_ids, cache))
         with decode_rows_scope(self.decode_rows):
-            for i, blk in enumerate(self.h):
-                x = blk(x, fc, attention_mask, segment_ids, position_ids, None if cache is None else cache[i], layout)
+            x = self._blocks(x, fc, attention_mask, segment_ids, position_ids, cache, layout)
         return self.ln_f(x)
+
+    def _blocks(self, x, fc, attention_mask, segment_ids, position_ids, cache, layout):
+        """the blocks in turn; with remat_blocks on, an uncached block call that autograd records goes through
+        lwm_amd.remat.remat_block (every other call is the plain one: remat.applies)"""
+        remat = cache is None and self.remat_blocks
+        for i, blk in enumerate(self.h):
+            if remat and _remat.applies(blk, x):
+                x = _remat.remat_block(blk, x, fc, attention_mask, segment_ids, position_ids, layout)
+            else:
+                x = blk(x, fc, attention_mask, segment_ids, position_ids, None if cache is None else cache[i], layout)
+        return x
 
     def _fused_decode_ok(self, x, n_sp):
         """One token per batch row through the KV cache, bf16, no autograd, one rank: the layers can run as GEMV launch

@@ -662,7 +662,9 @@ def _relayout(kernels):
 
 
 def fused_dense_ok(x, kernels):
-    """The fused / re-laid path serves bf16 GEMMs on the device with more rows than a decode step has."""
+    """The fused / re-laid path serves bf16 GEMMs on the device with more rows than a decode step has.  (Its `_relayout`
+    caches -- re-laid copies of the projections, about 22 GB at LWM-7B -- are the largest fixed cost left in a step that
+    runs with remat_blocks, lwm_amd/remat.py.)"""
     return (_os.environ.get("LWM_DENSE_FUSED", "1") == "1" and x.is_cuda and x.dtype == torch.bfloat16 and
             x.numel() // x.shape[-1] > 4 and
             all(k.is_cuda and k.dtype == torch.bfloat16 and k.is_contiguous() and k.dim() == 2 and

@@ -41,7 +41,7 @@ import os
 import torch
 import torch.distributed as dist
 
-from . import ops as _ops
+from . import ops as _ops, remat as _remat
 
 
 # ----------------------------------------------------------------- layouts
@@ -837,8 +837,15 @@ class _RingAttention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, segment_ids, key_valid, cfg):
         block, comm, layout, causal, scale = cfg
-        out, lses = ring_forward(block, comm, q, k, v, layout=layout, causal=causal,
-                                 segment_ids=segment_ids, key_valid=key_valid, scale=scale)
+        # the recompute of a remat block (lwm_amd/remat.py) gets the recorded out / lses of its forward back: nothing is
+        # launched and nothing is exchanged, on any rank; the recomputed q, k, v are saved beside them
+        kept = _remat.attention_replay(q)
+        if kept is None:
+            out, lses = ring_forward(block, comm, q, k, v, layout=layout, causal=causal,
+                                     segment_ids=segment_ids, key_valid=key_valid, scale=scale)
+            _remat.attention_record(out, lses)
+        else:
+            out, lses = kept
         ctx.save_for_backward(q, k, v, out, *lses)
         ctx.cfg = cfg
         ctx.masks = (segment_ids, key_valid)

@@ -17,7 +17,7 @@ import ctypes as C
 
 import torch
 
-from . import _capi
+from . import _capi, remat as _remat
 from ._lib import lib
 from .ops import _t4
 
@@ -366,9 +366,16 @@ class _RingAttentionC(torch.autograd.Function):
     def forward(ctx, q, k, v, ring, causal, segment_ids, key_valid, scale, layout):
         # (None beyond the budget -- the backward fetches again -- and when nothing asks for a gradient: a no_grad / eval
         #  forward has no backward to keep the K/V for.  ctx.needs_input_grad is the same on every rank of a model.)
-        keep = ring.kv_keep_buffer(q) if any(ctx.needs_input_grad[:3]) else None
-        out, lse = ring.forward(q, k, v, causal=causal, segment_ids=segment_ids, key_valid=key_valid, scale=scale, layout=layout,
-                                kv_keep=keep)
+        # the recompute of a remat block (lwm_amd/remat.py) gets its forward's out / lse back: no launch, no exchange and
+        # no kv_keep buffer on any rank -- its backward fetches K/V again
+        kept = _remat.attention_replay(q)
+        if kept is None:
+            keep = ring.kv_keep_buffer(q) if any(ctx.needs_input_grad[:3]) else None
+            out, lse = ring.forward(q, k, v, causal=causal, segment_ids=segment_ids, key_valid=key_valid, scale=scale,
+                                    layout=layout, kv_keep=keep)
+            _remat.attention_record(out, (lse,))
+        else:
+            keep, (out, (lse,)) = None, kept
         ctx.save_for_backward(q, k, v, out, lse)
         ctx.cfg = (ring, causal, segment_ids, key_valid, scale, layout)
         # the gathered K/V of this layer, kept for its backward -- only when the call took the gathered form (else the

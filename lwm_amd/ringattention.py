@@ -11,6 +11,7 @@ import os
 
 import torch
 
+from . import remat as _remat
 from .ring import (HipBlockOps, SeqLayout, SingleComm, TorchRingComm, cache_update, ring_attention,
                    ring_inference)
 
@@ -239,7 +240,9 @@ def blockwise_feedforward(module, x, chunk_size, pre_remat=True):
     S = x.shape[1]
 
     def run(c):
-        if pre_remat and torch.is_grad_enabled() and c.requires_grad:
+        # (inside the recompute of a remat block -- lwm_amd/remat.py -- the chunks run plainly: the block is being
+        #  recomputed already, and a checkpoint here would run the MLP a third time)
+        if pre_remat and torch.is_grad_enabled() and c.requires_grad and not _remat.recomputing():
             from torch.utils.checkpoint import checkpoint
             return checkpoint(module, c, use_reentrant=False)
         return module(c)

@@ -60,10 +60,7 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
             # opt-in (decode_rows / LWM_DECODE_ROWS): a cached one-token step of sample_mode 'text' / 'vision' takes the
             # fused step of the text model at any row count the option covers -- and with it the 8-bit packs
             return self._layers(x, n_sp, attention_mask, segment_ids, position_ids, cache, layout)
-        fc = self._table(x.device)
-        for i, blk in enumerate(self.h):
-            x = blk(x, fc, attention_mask, segment_ids, position_ids, None if cache is None else cache[i], layout)
-        return self.ln_f(x)
+        return self.ln_f(self._blocks(x, self._table(x.device), attention_mask, segment_ids, position_ids, cache, layout))
 
     def _decode_weight_params(self):
         """... and the vision head where it is a parameter of its own (the tied head is a transposed view of vte and
