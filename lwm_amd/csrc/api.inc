@@ -136,18 +136,12 @@ static int kvq_cache_write(const char* name, const char* kname, void (*kernel)(P
     return launch(kname, kernel, (long)(blocks > 16384 ? 16384 : blocks), 256, 0, stream, p);
 }
 
-// head_bytes > 0: the strides are checked too (non-negative, a head no smaller than that).  scales_f32: the scale
-// pointers are checked for 4-byte alignment with lse_acc.  row_align: 16, or 8 where a lane's part of a row is loaded in
-// 8-byte words.
-template <class F, class P, class Args>
-static int kvq_attn_decode(const char* name, void (*kernel)(P), int ecode, int head_bytes, bool scales_f32, int row_align,
-                           const Args* a, void* stream) {
-    if (!a) return fail(LWM_EINVAL, "%s: args is null", name);
-    int r;
-    if ((r = check_t4("q", a->q, true))) return r;
-    if (a->D != kHeadDim) return fail(ecode, "%s: head_dim %ld (only 128)", name, a->D);
-    if (a->B < 0 || a->Sk < 0 || a->H <= 0) return fail(LWM_EINVAL, "%s: bad dimension", name);
-    if (!(a->scale > 0.0f)) return fail(LWM_EINVAL, "%s: scale must be > 0", name);
+// What the decode and the block entries check of the cache, the outputs and k_splits, in this order.  ecode: what an
+// alignment refusal returns.  head_bytes > 0: the strides are checked too (non-negative, a head no smaller than that).
+// scales_f32: the scale pointers are checked for 4-byte alignment with lse_acc.  row_align: 16, or 8 where a lane's part
+// of a row is loaded in 8-byte words.
+template <class Args>
+static int kvq_check_cache(const char* name, int ecode, int head_bytes, bool scales_f32, int row_align, const Args* a) {
     if (!a->k || !a->v || !a->k_scale || !a->v_scale || !a->out_acc || !a->lse_acc)
         return fail(LWM_EINVAL, "%s: null pointer (k, v, k_scale, v_scale, out_acc, lse_acc)", name);
     if (!aligned16(a->out_acc) || (((uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->k_stride_b | (uintptr_t)a->k_stride_s |
@@ -162,6 +156,21 @@ static int kvq_attn_decode(const char* name, void (*kernel)(P), int ecode, int h
     if (((scales_f32 ? (uintptr_t)a->k_scale | (uintptr_t)a->v_scale : 0) | (uintptr_t)a->lse_acc) & 3)
         return fail(ecode, scales_f32 ? "%s: scales and lse_acc must be 4-byte aligned" : "%s: lse_acc must be 4-byte aligned", name);
     if (a->k_splits < 0 || a->k_splits > 4096) return fail(LWM_EINVAL, "%s: k_splits out of range", name);
+    return 0;
+}
+
+// ecode: what the shape and alignment refusals of the entry return.  head_bytes (> 0: the strides are checked too),
+// scales_f32 and row_align (16, or 8 for rows loaded in 8-byte words): passed on to kvq_check_cache above.
+template <class F, class P, class Args>
+static int kvq_attn_decode(const char* name, void (*kernel)(P), int ecode, int head_bytes, bool scales_f32, int row_align,
+                           const Args* a, void* stream) {
+    if (!a) return fail(LWM_EINVAL, "%s: args is null", name);
+    int r;
+    if ((r = check_t4("q", a->q, true))) return r;
+    if (a->D != kHeadDim) return fail(ecode, "%s: head_dim %ld (only 128)", name, a->D);
+    if (a->B < 0 || a->Sk < 0 || a->H <= 0) return fail(LWM_EINVAL, "%s: bad dimension", name);
+    if (!(a->scale > 0.0f)) return fail(LWM_EINVAL, "%s: scale must be > 0", name);
+    if ((r = kvq_check_cache(name, ecode, head_bytes, scales_f32, row_align, a))) return r;
     if (a->B == 0) return LWM_OK;
     P p;
     p.q = (const bf16_t*)a->q.ptr; p.q_sb = a->q.stride_b; p.q_sh = a->q.stride_h;
@@ -175,6 +184,39 @@ static int kvq_attn_decode(const char* name, void (*kernel)(P), int ecode, int h
     p.B = a->B; p.Sk = a->Sk; p.H = a->H; p.k_splits = a->k_splits > 1 ? a->k_splits : 1;
     p.scale = a->scale; p.out_acc = a->out_acc; p.lse_acc = a->lse_acc;
     return launch(name, kernel, (long)p.B * p.k_splits, kDecThreads, kDecqLdsBytes<F>, stream, p);
+}
+
+// The block kernels over the quantised caches (attn_prefill_kv8.h, attn_prefill_kv6.h; P = KvqPrefillParams<scale type>):
+// both entries refuse a head_dim and an alignment with LWM_EUNSUPPORTED (the kv6 DECODE entry returns LWM_EINVAL).
+template <class P, class Args>
+static int kvq_attn_prefill(const char* name, void (*kernel)(P), int head_bytes, bool scales_f32, int row_align, const Args* a,
+                            void* stream) {
+    if (!a) return fail(LWM_EINVAL, "%s: args is null", name);
+    int r;
+    if ((r = check_t4("q", a->q, true))) return r;
+    if (a->D != kHeadDim) return fail(LWM_EUNSUPPORTED, "%s: head_dim %ld (only 128)", name, a->D);
+    if (a->B < 0 || a->Sq < 1 || a->Sk < 1 || a->H <= 0 || a->q_start < 0)
+        return fail(LWM_EINVAL, "%s: bad dimension (B >= 0, Sq >= 1, Sk >= 1, H >= 1, q_start >= 0)", name);
+    if (!(a->scale > 0.0f)) return fail(LWM_EINVAL, "%s: scale must be > 0", name);
+    if ((r = kvq_check_cache(name, LWM_EUNSUPPORTED, head_bytes, scales_f32, row_align, a))) return r;
+    if (a->B == 0) return LWM_OK;
+    P p;
+    memset(&p, 0, sizeof(p));
+    p.a.q = (const bf16_t*)a->q.ptr; p.a.q_sb = a->q.stride_b; p.a.q_ss = a->q.stride_s; p.a.q_sh = a->q.stride_h;
+    p.a.out_acc = a->out_acc; p.a.lse_acc = a->lse_acc; p.a.key_valid = a->key_valid;
+    p.a.B = a->B; p.a.H = a->H; p.a.Sq = a->Sq; p.a.Sk = a->Sk;
+    p.a.q_start = a->q_start; p.a.k_start = 0; p.a.q_np = 1; p.a.k_np = 1;
+    p.a.scale = a->scale; p.a.causal = 1; p.a.carry_in = 0; p.a.final_out = 0;
+    p.a.k_splits = a->k_splits > 1 ? a->k_splits : 1;
+    p.k = (const uint8_t*)a->k; p.v = (const uint8_t*)a->v;
+    p.k_scale = (decltype(p.k_scale))a->k_scale; p.v_scale = (decltype(p.v_scale))a->v_scale;
+    p.k_sb = a->k_stride_b; p.k_ss = a->k_stride_s; p.k_sh = a->k_stride_h;
+    p.v_sb = a->v_stride_b; p.v_ss = a->v_stride_s; p.v_sh = a->v_stride_h;
+    p.ks_sb = a->k_scale_stride_b; p.ks_ss = a->k_scale_stride_s;
+    p.vs_sb = a->v_scale_stride_b; p.vs_ss = a->v_scale_stride_s;
+    p.kv_sb = a->key_valid_stride_b;
+    const long nqt = (p.a.Sq + kFwdBQ - 1) / kFwdBQ;
+    return launch(name, kernel, nqt * p.a.H * p.a.B * p.a.k_splits, kFwdThreads, kFwdLdsBytes, stream, p);
 }
 
 }  // namespace lwm
@@ -351,81 +393,11 @@ int lwm_attn_decode_kv6(const LwmKv6DecodeArgs* a, void* stream) {
 }
 
 int lwm_attn_prefill_kv6(const LwmKv6PrefillArgs* a, void* stream) {
-    using namespace lwm;
-    if (!a) return fail(LWM_EINVAL, "%s", "attn_prefill_kv6: args is null");
-    int r;
-    if ((r = check_t4("q", a->q, true))) return r;
-    if (a->D != kHeadDim) return fail(LWM_EUNSUPPORTED, "%s: head_dim %ld (only 128)", "attn_prefill_kv6", a->D);
-    if (a->B < 0 || a->Sq < 1 || a->Sk < 1 || a->H <= 0 || a->q_start < 0)
-        return fail(LWM_EINVAL, "%s", "attn_prefill_kv6: bad dimension (B >= 0, Sq >= 1, Sk >= 1, H >= 1, q_start >= 0)");
-    if (!(a->scale > 0.0f)) return fail(LWM_EINVAL, "%s", "attn_prefill_kv6: scale must be > 0");
-    if (!a->k || !a->v || !a->k_scale || !a->v_scale || !a->out_acc || !a->lse_acc)
-        return fail(LWM_EINVAL, "%s", "attn_prefill_kv6: null pointer (k, v, k_scale, v_scale, out_acc, lse_acc)");
-    if (!aligned16(a->out_acc) || (((uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->k_stride_b | (uintptr_t)a->k_stride_s |
-                                    (uintptr_t)a->k_stride_h | (uintptr_t)a->v_stride_b | (uintptr_t)a->v_stride_s |
-                                    (uintptr_t)a->v_stride_h) & 7))
-        return fail(LWM_EUNSUPPORTED, "%s", "attn_prefill_kv6: cache rows must be 8-byte and out_acc 16-byte aligned (pointers and strides)");
-    if (a->k_stride_s < 0 || a->v_stride_s < 0 || a->k_stride_h < 96 || a->v_stride_h < 96 || a->k_scale_stride_s < 0 ||
-        a->v_scale_stride_s < 0 || a->k_scale_stride_b < 0 || a->v_scale_stride_b < 0 || a->k_stride_b < 0 || a->v_stride_b < 0)
-        return fail(LWM_EINVAL, "%s", "attn_prefill_kv6: bad strides (non-negative; a head is 96 bytes)");
-    if (((uintptr_t)a->lse_acc) & 3) return fail(LWM_EUNSUPPORTED, "%s", "attn_prefill_kv6: lse_acc must be 4-byte aligned");
-    if (a->k_splits < 0 || a->k_splits > 4096) return fail(LWM_EINVAL, "%s", "attn_prefill_kv6: k_splits out of range");
-    if (a->B == 0) return LWM_OK;
-    Kv6PrefillParams p;
-    memset(&p, 0, sizeof(p));
-    p.a.q = (const bf16_t*)a->q.ptr; p.a.q_sb = a->q.stride_b; p.a.q_ss = a->q.stride_s; p.a.q_sh = a->q.stride_h;
-    p.a.out_acc = a->out_acc; p.a.lse_acc = a->lse_acc; p.a.key_valid = a->key_valid;
-    p.a.B = a->B; p.a.H = a->H; p.a.Sq = a->Sq; p.a.Sk = a->Sk;
-    p.a.q_start = a->q_start; p.a.k_start = 0; p.a.q_np = 1; p.a.k_np = 1;
-    p.a.scale = a->scale; p.a.causal = 1; p.a.carry_in = 0; p.a.final_out = 0;
-    p.a.k_splits = a->k_splits > 1 ? a->k_splits : 1;
-    p.k6 = (const uint8_t*)a->k; p.v6 = (const uint8_t*)a->v;
-    p.k_scale = (const uint8_t*)a->k_scale; p.v_scale = (const uint8_t*)a->v_scale;
-    p.k6_sb = a->k_stride_b; p.k6_ss = a->k_stride_s; p.k6_sh = a->k_stride_h;
-    p.v6_sb = a->v_stride_b; p.v6_ss = a->v_stride_s; p.v6_sh = a->v_stride_h;
-    p.ks_sb = a->k_scale_stride_b; p.ks_ss = a->k_scale_stride_s;
-    p.vs_sb = a->v_scale_stride_b; p.vs_ss = a->v_scale_stride_s;
-    p.kv_sb = a->key_valid_stride_b;
-    const long nqt = (p.a.Sq + kFwdBQ - 1) / kFwdBQ;
-    return launch("attn_prefill_kv6", attn_prefill_kv6_kernel, nqt * p.a.H * p.a.B * p.a.k_splits, kFwdThreads, kFwdLdsBytes,
-                  stream, p);
+    return lwm::kvq_attn_prefill("attn_prefill_kv6", lwm::attn_prefill_kv6_kernel, 96, false, 8, a, stream);
 }
 
 int lwm_attn_prefill_kv8(const LwmKv8PrefillArgs* a, void* stream) {
-    using namespace lwm;
-    if (!a) return fail(LWM_EINVAL, "%s", "attn_prefill_kv8: args is null");
-    int r;
-    if ((r = check_t4("q", a->q, true))) return r;
-    if (a->D != kHeadDim) return fail(LWM_EUNSUPPORTED, "%s: head_dim %ld (only 128)", "attn_prefill_kv8", a->D);
-    if (a->B < 0 || a->Sq < 1 || a->Sk < 1 || a->H <= 0 || a->q_start < 0)
-        return fail(LWM_EINVAL, "%s", "attn_prefill_kv8: bad dimension (B >= 0, Sq >= 1, Sk >= 1, H >= 1, q_start >= 0)");
-    if (!(a->scale > 0.0f)) return fail(LWM_EINVAL, "%s", "attn_prefill_kv8: scale must be > 0");
-    if (!a->k || !a->v || !a->k_scale || !a->v_scale || !a->out_acc || !a->lse_acc)
-        return fail(LWM_EINVAL, "%s", "attn_prefill_kv8: null pointer (k, v, k_scale, v_scale, out_acc, lse_acc)");
-    if (!aligned16(a->k) || !aligned16(a->v) || !aligned16(a->out_acc) || ((a->k_stride_b | a->k_stride_s | a->k_stride_h |
-                                                                          a->v_stride_b | a->v_stride_s | a->v_stride_h) & 15))
-        return fail(LWM_EUNSUPPORTED, "%s", "attn_prefill_kv8: cache rows and out_acc must be 16-byte aligned (pointers and strides)");
-    if ((((uintptr_t)a->k_scale | (uintptr_t)a->v_scale | (uintptr_t)a->lse_acc) & 3))
-        return fail(LWM_EUNSUPPORTED, "%s", "attn_prefill_kv8: scales and lse_acc must be 4-byte aligned");
-    if (a->k_splits < 0 || a->k_splits > 4096) return fail(LWM_EINVAL, "%s", "attn_prefill_kv8: k_splits out of range");
-    if (a->B == 0) return LWM_OK;
-    Kv8PrefillParams p;
-    memset(&p, 0, sizeof(p));
-    p.a.q = (const bf16_t*)a->q.ptr; p.a.q_sb = a->q.stride_b; p.a.q_ss = a->q.stride_s; p.a.q_sh = a->q.stride_h;
-    p.a.out_acc = a->out_acc; p.a.lse_acc = a->lse_acc; p.a.key_valid = a->key_valid;
-    p.a.B = a->B; p.a.H = a->H; p.a.Sq = a->Sq; p.a.Sk = a->Sk;
-    p.a.q_start = a->q_start; p.a.k_start = 0; p.a.q_np = 1; p.a.k_np = 1;
-    p.a.scale = a->scale; p.a.causal = 1; p.a.carry_in = 0; p.a.final_out = 0;
-    p.a.k_splits = a->k_splits > 1 ? a->k_splits : 1;
-    p.k8 = (const uint8_t*)a->k; p.v8 = (const uint8_t*)a->v; p.k_scale = a->k_scale; p.v_scale = a->v_scale;
-    p.k8_sb = a->k_stride_b; p.k8_ss = a->k_stride_s; p.k8_sh = a->k_stride_h;
-    p.v8_sb = a->v_stride_b; p.v8_ss = a->v_stride_s; p.v8_sh = a->v_stride_h;
-    p.ks_sb = a->k_scale_stride_b; p.ks_ss = a->k_scale_stride_s;
-    p.vs_sb = a->v_scale_stride_b; p.vs_ss = a->v_scale_stride_s;
-    p.kv_sb = a->key_valid_stride_b;
-    const long nqt = (p.a.Sq + kFwdBQ - 1) / kFwdBQ;
-    return launch("attn_prefill_kv8", attn_prefill_kv8_kernel, nqt * p.a.H * p.a.B * p.a.k_splits, kFwdThreads, kFwdLdsBytes,
-                  stream, p);
+    return lwm::kvq_attn_prefill("attn_prefill_kv8", lwm::attn_prefill_kv8_kernel, 0, true, 16, a, stream);
 }
 
 static int check_bwd(const LwmAttnArgs* a) {

@@ -37,6 +37,11 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 LWM_DEVICE f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return f32x2{fmaf(a[0], b[0], c[0]), fmaf(a[1], b[1], c[1])}; }
 LWM_DEVICE f32x2 mad2(f32x2 a, f32x2 b, f32x2 c) { return a * b + c; }
 LWM_DEVICE void global_store_b32(void* p, uint32_t v) { memcpy(p, &v, 4); }
+LWM_DEVICE u32x2 global_load_b64(const void* p) {
+    u32x2 v;
+    memcpy(&v, p, 8);
+    return v;
+}
 #else
 // v_pk_fma_f32: the register pairs a packed conversion leaves are its operands as they are
 LWM_DEVICE f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
@@ -44,6 +49,7 @@ LWM_DEVICE f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_
 // rounds the product.)  For sums of TWO products, where the compiler would choose which one to round.
 LWM_DEVICE f32x2 mad2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
 LWM_DEVICE void global_store_b32(void* p, uint32_t v) { *(uint32_t*)p = v; }
+LWM_DEVICE u32x2 global_load_b64(const void* p) { return *(const u32x2*)p; }
 #endif
 // The loads written above this point are ISSUED above it: the optimiser may neither sink one below it (into the branch
 // of its first use, behind a wait for everything outstanding) nor hoist later work between them.  No instruction.

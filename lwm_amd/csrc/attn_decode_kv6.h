@@ -1,8 +1,7 @@
 // attn_decode_kv6.h -- a 6-bit (OCP MXFP6: e2m3 codes, one e8m0 scale per 32 elements) KV cache: the quantising cache
 // write and the cached-decode attention kernel that streams it.  Requires wave_ops.h + attn_common.h + attn_decode.h
-// (f32x2, global_load_u8) + attn_decode_kvq.h (the write and the kernel, over Kv6Format below) + attn_decode_kv4.h
-// (e8m0_to_f32 and the scale half of Kv4Format: the scale tensors of the two caches are the same) + attn_prefill_kv8.h
-// (global_load_b64).
+// (f32x2, global_load_u8, global_load_b64) + attn_decode_kvq.h (the write and the kernel, over Kv6Format below) +
+// attn_decode_kv4.h (e8m0_to_f32 and the scale half of Kv4Format: the scale tensors of the two caches are the same).
 //
 // Why: the 8-bit cache does not hold a million tokens on one GPU and the 4-bit cache pays for it in precision.  Per key
 // row and head this cache holds 96 bytes of codes and 4 scale bytes: 100 against 132 (attn_decode_kv8.h) and 68

@@ -1,6 +1,10 @@
 // attn_fwd.h -- blockwise attention forward for one (q block, kv block) ring
 // step on gfx950.  Requires wave_ops.h + attn_common.h.
 //
+// What is launched from here is the inference flavour (dense mask, split-K: attn_fwd_infer_kernel); the block kernels
+// over the quantised caches (attn_prefill_kv8.h, attn_prefill_kv6.h) call fwd_tile as it is.  The training forward is
+// attn_fwd64.h.
+//
 // Replaces the forward of `ringattention` as called at lwm/llama.py:539-569
 // (blockwise online-softmax update, fp32 logits, causal_block_size=1, masks per
 // lwm/llama.py:527-537 and :572-592).  One launch = the reference's whole
@@ -87,8 +91,6 @@ LWM_DEVICE void fwd_stage_write(const FwdCtx& cx, const FwdStage& st, int kt, in
 }
 
 // ---- the three phases of one 64-key tile against this wave's 32 queries.
-// INFER = the dense-mask / split-K flavour (ringattention_inference); the training
-// kernel is compiled without that code.
 
 // S^T = K Q^T  (rows = keys, cols = queries); K tile in LDS buffer BUF.
 // Fragment bases are re-derived per tile (XOR form, attn_common.h) and the K / V
@@ -124,7 +126,7 @@ LWM_DEVICE void fwd_phase_s(const FwdCtx& cx, const bf16x8 (&qf)[8], f32x16 (&st
 
 // masks + online softmax of the scores in st; leaves P^T (bf16) in pb and updates m_run, l_run, acc.
 // Key meta of the tile in meta buffer BUF.
-template <int BUF, bool INFER>
+template <int BUF>
 LWM_DEVICE void fwd_phase_softmax(const AttnParams& p, const FwdCtx& cx, int kt, f32x16 (&st)[2],
                                   bf16x8 (&pb)[2][2], float& m_run, float& l_run, f32x16 (&acc)[4]) {
     const int64_t k_pos0 = p.k_start + (int64_t)kt * kFwdBK;
@@ -156,7 +158,7 @@ LWM_DEVICE void fwd_phase_softmax(const AttnParams& p, const FwdCtx& cx, int kt,
             }
     }
     // ---- arbitrary boolean mask (ringattention_inference, lwm/llama.py:577-614)
-    if (INFER && cx.mask_row) {
+    if (cx.mask_row) {
         const uint8_t* mr = cx.mask_row + (int64_t)kt * kFwdBK;
         for (int kb2 = 0; kb2 < 2; ++kb2)
             for (int r = 0; r < 16; ++r) {
@@ -221,51 +223,35 @@ LWM_DEVICE void fwd_phase_pv(const FwdCtx& cx, const bf16x8 (&pb)[2][2], f32x16 
 }
 
 // true when the tile cannot contribute to this wave's rows (staging only)
-LWM_DEVICE bool fwd_wave_skips(const AttnParams& p, const FwdCtx& cx, int kt, bool infer) {
-    if (infer && cx.wave_idle) return true;           // short query blocks
+LWM_DEVICE bool fwd_wave_skips(const AttnParams& p, const FwdCtx& cx, int kt) {
+    if (cx.wave_idle) return true;                    // short query blocks
     return p.causal && p.k_start + (int64_t)kt * kFwdBK > cx.wq_max;   // wholly in this wave's future
 }
 
 // One 64-key tile held in LDS buffer BUF, the three phases back to back.
-template <int BUF, bool INFER>
+template <int BUF>
 LWM_DEVICE void fwd_tile(const AttnParams& p, const FwdCtx& cx, const bf16x8 (&qf)[8], int kt,
-                         float& m_run, float& l_run, f32x16 (&acc)[4], ProfAcc& pa) {
-    (void)pa;
-    PROF_DECL(4);
-    PROF_T(0);
-    if (fwd_wave_skips(p, cx, kt, INFER)) return;
+                         float& m_run, float& l_run, f32x16 (&acc)[4]) {
+    if (fwd_wave_skips(p, cx, kt)) return;
     f32x16 st[2];
     bf16x8 pb[2][2];
     fwd_phase_s<BUF>(cx, qf, st);
-    PROF_KEEP(st[1][15]);
-    PROF_T(1);
-    fwd_phase_softmax<BUF, INFER>(p, cx, kt, st, pb, m_run, l_run, acc);
-    PROF_KEEP(pb[1][1]);
-    PROF_T(2);
+    fwd_phase_softmax<BUF>(p, cx, kt, st, pb, m_run, l_run, acc);
     fwd_phase_pv<BUF>(cx, pb, acc);
-    PROF_KEEP(acc[3][0]);
-    PROF_T(3);
-    PROF_ADD(pa, 0, 0, 1);   // S = K Q^T
-    PROF_ADD(pa, 1, 1, 2);   // masks + softmax
-    PROF_ADD(pa, 2, 2, 3);   // O += V^T P^T
-#ifdef LWM_PROF
-    pa.v[5] += 1;
-#endif
 }
 
-template <bool INFER>
 LWM_DEVICE void attn_fwd_body(const AttnParams& p) {
     const lds_t lds = dyn_lds();
     const int tid = thread_idx();
     const int wave = tid >> 6, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
 
-    // ---- block -> (q tile, head, batch): longest q tiles first; all q tiles of
+    // ---- block -> (q tile, head, batch, split): longest q tiles first; all q tiles of
     // one (b,h) stay on one XCD (block b runs on XCD b%8) so its K/V stream is
     // shared in that XCD's L2.
     const int nqt = (p.Sq + kFwdBQ - 1) / kFwdBQ;
     const int HB = p.H * p.B;
-    const int nsplit = (INFER && p.k_splits > 1) ? p.k_splits : 1;
-    const int split = INFER ? block_idx_x() / (nqt * HB) : 0;
+    const int nsplit = p.k_splits > 1 ? p.k_splits : 1;
+    const int split = block_idx_x() / (nqt * HB);
     int lin = block_idx_x() - split * (nqt * HB), qt, hb;
     if ((HB & 7) == 0) {
         int xcd = lin & 7, i = lin >> 3;
@@ -308,8 +294,8 @@ LWM_DEVICE void attn_fwd_body(const AttnParams& p) {
     cx.wq_min = p.q_start + qt * kFwdBQ + wave * 32;
     cx.wq_max = cx.wq_min + 31;
     cx.c = p.scale * kLog2e;
-    cx.wave_idle = INFER && wave_uniform(qt * kFwdBQ + wave * 32 >= p.Sq ? 1 : 0) != 0;
-    cx.mask_row = (INFER && p.dense_mask && q_ok)
+    cx.wave_idle = wave_uniform(qt * kFwdBQ + wave * 32 >= p.Sq ? 1 : 0) != 0;
+    cx.mask_row = (p.dense_mask && q_ok)
                       ? p.dense_mask + (int64_t)b * p.msk_sb + (int64_t)q_row * p.msk_sq
                       : nullptr;
 
@@ -326,11 +312,6 @@ LWM_DEVICE void attn_fwd_body(const AttnParams& p) {
         }
     }
 
-    ProfAcc pa = {};
-    PROF_DECL(5);
-#ifdef LWM_PROF
-    const unsigned long long prof_k0 = __builtin_amdgcn_s_memtime();
-#endif
     float m_run = -INFINITY;  // running max of raw scores (q.k, unscaled)
     float l_run = 0.0f;       // this half-wave's partial row sum
     f32x16 acc[4];
@@ -367,29 +348,18 @@ LWM_DEVICE void attn_fwd_body(const AttnParams& p) {
         for (int kt = kt0; kt < nkt; kt += 2) {
             const bool more1 = kt + 1 < nkt;
             if (more1) fwd_stage_load(p, kb, vb, b, kt + 1, tid, stg);
-            fwd_tile<0, INFER>(p, cx, qf, kt, m_run, l_run, acc, pa);
-            PROF_T(0);
+            fwd_tile<0>(p, cx, qf, kt, m_run, l_run, acc);
             if (more1) fwd_stage_write<1>(cx, stg, kt + 1, p.Sk);
-            PROF_T(1);
             block_sync();
-            PROF_T(2);
-            PROF_ADD(pa, 3, 0, 1);   // staging ds_writes (every second tile is sampled)
-            PROF_ADD(pa, 4, 1, 2);   // barrier wait
             if (!more1) break;
             const bool more2 = kt + 2 < nkt;
             if (more2) fwd_stage_load(p, kb, vb, b, kt + 2, tid, stg);
-            fwd_tile<1, INFER>(p, cx, qf, kt + 1, m_run, l_run, acc, pa);
+            fwd_tile<1>(p, cx, qf, kt + 1, m_run, l_run, acc);
             if (more2) fwd_stage_write<0>(cx, stg, kt + 2, p.Sk);
             block_sync();
         }
     }
 
-#ifdef LWM_PROF
-    if (!INFER && hb == 0 && qt == nqt - 1 && lane == 0 && p.out_acc) {   // the longest q tile of head 0
-        pa.v[6] = __builtin_amdgcn_s_memtime() - prof_k0;
-        *((ProfAcc*)p.out_acc + wave) = pa;
-    }
-#endif
     // ---- epilogue: normalise, merge with the ring carry, store
     const float l_tot = l_run + xhalf(l_run);
     float inv = 0.0f, lse_b = -INFINITY;
@@ -444,7 +414,6 @@ LWM_DEVICE void attn_fwd_body(const AttnParams& p) {
     }
 }
 
-LWM_KERNEL(kFwdThreads) void attn_fwd_kernel(AttnParams p) { attn_fwd_body<false>(p); }
-LWM_KERNEL(kFwdThreads) void attn_fwd_infer_kernel(AttnParams p) { attn_fwd_body<true>(p); }
+LWM_KERNEL(kFwdThreads) void attn_fwd_infer_kernel(AttnParams p) { attn_fwd_body(p); }
 
 }  // namespace lwm

@@ -1,9 +1,10 @@
 // attn_prefill_kv6.h -- attention of a BLOCK of queries over the 6-bit (MXFP6 e2m3) KV cache: chunked prefill, a
-// follow-up turn, a block appended to a live cache.  Requires wave_ops.h + attn_common.h + attn_fwd.h + attn_decode.h +
-// attn_decode_kv6.h (the format, cvt_e2m3x32_bf16, e8m0_to_f32) + attn_prefill_kv8.h (global_load_b64).
+// follow-up turn, a block appended to a live cache.  Requires wave_ops.h + attn_common.h + attn_fwd.h + attn_decode.h
+// (global_load_u8, global_load_b64) + attn_decode_kv6.h (the format, cvt_e2m3x32_bf16, e8m0_to_f32) +
+// attn_prefill_kv8.h (KvqPrefillParams).
 //
 // The kernel is attn_prefill_kv8.h with another staging: the same workgroup -> (q tile, head, batch, split) map, causal
-// tile range, split walk, fwd_tile<BUF, true> and epilogue.  K and V arrive as 24-byte blocks of e2m3 codes with one e8m0
+// tile range, split walk, fwd_tile<BUF> and epilogue.  K and V arrive as 24-byte blocks of e2m3 codes with one e8m0
 // byte each and are dequantised between the global load and the LDS write; q * s is exactly representable in bf16
 // (attn_decode_kv6.h), so the LDS tiles are bit for bit the tiles attn_fwd_body stages from a bf16 copy of the cache.
 // No bf16 copy of a cache row ever exists in HBM.
@@ -17,18 +18,8 @@
 
 namespace lwm {
 
-struct Kv6PrefillParams {
-    AttnParams a;              // as Kv8PrefillParams
-    const uint8_t* k6;         // e2m3 blocks (B,Sk,H,96)
-    const uint8_t* v6;
-    const uint8_t* k_scale;    // e8m0 bytes (B,Sk,H,4)
-    const uint8_t* v_scale;
-    int64_t k6_sb, k6_ss, k6_sh;   // bytes
-    int64_t v6_sb, v6_ss, v6_sh;
-    int64_t ks_sb, ks_ss;      // bytes; the 4 bytes of a head and the heads of a row contiguous
-    int64_t vs_sb, vs_ss;
-    int64_t kv_sb;             // key_valid: bytes between batch rows
-};
+// k, v: e2m3 blocks (B,Sk,H,96); k_scale, v_scale: e8m0 bytes (B,Sk,H,4)
+typedef KvqPrefillParams<uint8_t> Kv6PrefillParams;
 
 // what one thread holds of the next tile between its loads and its LDS writes
 struct Fwd6Stage {
@@ -80,7 +71,7 @@ LWM_KERNEL(kFwdThreads) void attn_prefill_kv6_kernel(Kv6PrefillParams pp) {
     const int tid = thread_idx();
     const int wave = tid >> 6, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
 
-    // ---- block -> (q tile, head, batch, split): as attn_fwd_body<true>
+    // ---- block -> (q tile, head, batch, split): as attn_fwd_body
     const int nqt = (p.Sq + kFwdBQ - 1) / kFwdBQ;
     const int HB = p.H * p.B;
     const int nsplit = p.k_splits > 1 ? p.k_splits : 1;
@@ -101,9 +92,9 @@ LWM_KERNEL(kFwdThreads) void attn_prefill_kv6_kernel(Kv6PrefillParams pp) {
     // ---- this thread's staging item: waves 0-3 stage K, waves 4-7 V (a wave-uniform choice)
     const bool st_v = tid >= 256;
     const int st_row = (tid & 255) >> 2, st_blk = tid & 3;
-    const uint8_t* cb = (st_v ? pp.v6 + (int64_t)b * pp.v6_sb + (int64_t)h * pp.v6_sh : pp.k6 + (int64_t)b * pp.k6_sb + (int64_t)h * pp.k6_sh) + st_blk * 24;
+    const uint8_t* cb = (st_v ? pp.v + (int64_t)b * pp.v_sb + (int64_t)h * pp.v_sh : pp.k + (int64_t)b * pp.k_sb + (int64_t)h * pp.k_sh) + st_blk * 24;
     const uint8_t* sb = (st_v ? pp.v_scale + (int64_t)b * pp.vs_sb : pp.k_scale + (int64_t)b * pp.ks_sb) + h * 4 + st_blk;
-    const int64_t c_ss = st_v ? pp.v6_ss : pp.k6_ss, s_ss = st_v ? pp.vs_ss : pp.ks_ss;
+    const int64_t c_ss = st_v ? pp.v_ss : pp.k_ss, s_ss = st_v ? pp.vs_ss : pp.ks_ss;
     lds_t slot_w[4];
     for (int j = 0; j < 4; ++j) slot_w[j] = lds + (st_v ? 2 * kFwdTileBytes : 0) + tile_off(st_row, 4 * st_blk + j);
 
@@ -157,7 +148,6 @@ LWM_KERNEL(kFwdThreads) void attn_prefill_kv6_kernel(Kv6PrefillParams pp) {
         nkt = nkt < s1 ? nkt : s1;
     }
 
-    ProfAcc pa = {};
     float m_run = -INFINITY;  // running max of raw scores (q.k, unscaled)
     float l_run = 0.0f;       // this half-wave's partial row sum
     f32x16 acc[4];
@@ -173,13 +163,13 @@ LWM_KERNEL(kFwdThreads) void attn_prefill_kv6_kernel(Kv6PrefillParams pp) {
         for (int kt = kt0; kt < nkt; kt += 2) {
             const bool more1 = kt + 1 < nkt;
             if (more1) fwd6_stage_load(p.Sk, cb, c_ss, sb, s_ss, kvb, kt + 1, tid, stg);
-            fwd_tile<0, true>(p, cx, qf, kt, m_run, l_run, acc, pa);
+            fwd_tile<0>(p, cx, qf, kt, m_run, l_run, acc);
             if (more1) fwd6_stage_write<1>(cx, slot_w, stg, kt + 1, p.Sk, has_valid);
             block_sync();
             if (!more1) break;
             const bool more2 = kt + 2 < nkt;
             if (more2) fwd6_stage_load(p.Sk, cb, c_ss, sb, s_ss, kvb, kt + 2, tid, stg);
-            fwd_tile<1, true>(p, cx, qf, kt + 1, m_run, l_run, acc, pa);
+            fwd_tile<1>(p, cx, qf, kt + 1, m_run, l_run, acc);
             if (more2) fwd6_stage_write<0>(cx, slot_w, stg, kt + 2, p.Sk, has_valid);
             block_sync();
         }

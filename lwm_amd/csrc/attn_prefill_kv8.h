@@ -1,10 +1,11 @@
 // attn_prefill_kv8.h -- attention of a BLOCK of queries over the 8-bit (e4m3) KV cache: chunked prefill, a follow-up
 // turn, a block appended to a live cache.  Requires wave_ops.h + attn_common.h + attn_fwd.h + attn_decode.h
-// (f32x2, issue_fence, global_load_u8, global_load_f32) + attn_decode_kv8.h (the format, cvt_e4m3x2_lo/hi).
+// (f32x2, issue_fence, global_load_u8, global_load_f32, global_load_b64) + attn_decode_kv8.h (the format,
+// cvt_e4m3x2_lo/hi).
 //
-// The kernel is attn_fwd_body<true> (attn_fwd.h) in its split-K partials form -- 512 threads, 256 queries per workgroup,
+// The kernel is attn_fwd_body (attn_fwd.h) in its split-K partials form -- 512 threads, 256 queries per workgroup,
 // 64-key LDS tiles, the same workgroup -> (q tile, head, batch, split) map, causal tile range and split walk, and
-// fwd_tile<BUF, true> (fwd_phase_s / fwd_phase_softmax / fwd_phase_pv) called as it is -- with ONE part replaced: the
+// fwd_tile<BUF> (fwd_phase_s / fwd_phase_softmax / fwd_phase_pv) called as it is -- with ONE part replaced: the
 // staging.  K and V arrive as e4m3 bytes with one f32 scale per (row, head) and are dequantised between the global load
 // and the LDS write; q * s is exactly representable in bf16 (attn_decode_kv8.h), so the LDS tiles are bit for bit the
 // tiles attn_fwd_body stages from a bf16 copy of the cache, and everything after the staging is the arithmetic of that
@@ -17,29 +18,22 @@
 
 namespace lwm {
 
-// ---- primitives of this header (the shared vocabulary of wave_ops.h is pinned to the counter profile)
-#ifdef LWM_EMU
-LWM_DEVICE u32x2 global_load_b64(const void* p) {
-    u32x2 v;
-    memcpy(&v, p, 8);
-    return v;
-}
-#else
-LWM_DEVICE u32x2 global_load_b64(const void* p) { return *(const u32x2*)p; }
-#endif
-
-struct Kv8PrefillParams {
+// The parameters of a block kernel over a quantised cache whose scales are scale_t (here float, one per (row, head);
+// attn_prefill_kv6.h: e8m0 bytes, 4 per (row, head)).  One struct, so that api.inc fills it in one place.
+template <class scale_t>
+struct KvqPrefillParams {
     AttnParams a;              // q, out_acc, lse_acc, key_valid, B/H/Sq/Sk, q_start, scale, k_splits; causal = 1, final_out = carry_in = 0
-    const uint8_t* k8;         // e4m3 bytes (B,Sk,H,128)
-    const uint8_t* v8;
-    const float* k_scale;      // (B,Sk,H)
-    const float* v_scale;
-    int64_t k8_sb, k8_ss, k8_sh;   // bytes
-    int64_t v8_sb, v8_ss, v8_sh;
-    int64_t ks_sb, ks_ss;      // floats; heads contiguous
+    const uint8_t* k;          // codes (B,Sk,H,head bytes)
+    const uint8_t* v;
+    const scale_t* k_scale;    // (B,Sk,H [, scales per head])
+    const scale_t* v_scale;
+    int64_t k_sb, k_ss, k_sh;  // bytes
+    int64_t v_sb, v_ss, v_sh;
+    int64_t ks_sb, ks_ss;      // scale_t elements; the scales of a head and the heads of a row contiguous
     int64_t vs_sb, vs_ss;
     int64_t kv_sb;             // key_valid: bytes between batch rows
 };
+typedef KvqPrefillParams<float> Kv8PrefillParams;
 
 // what one thread holds of the next tile between its loads and its LDS writes: 8 K bytes and 8 V bytes of each of its
 // two rows (attn_fwd.h: 16 bytes of bf16 each), the rows' scales and validity bytes; threads < 64 also the key-meta byte
@@ -70,9 +64,9 @@ LWM_DEVICE void fwd8_stage_load(const Kv8PrefillParams& p, const uint8_t* kb, co
         const int row = c >> 4, slot = c & 15;
         const int krow = kt * kFwdBK + row;
         const int kr = krow < Sk ? krow : Sk - 1;
-        const uint8_t* kp = kb + (int64_t)kr * p.k8_ss + slot * 8;
+        const uint8_t* kp = kb + (int64_t)kr * p.k_ss + slot * 8;
         st.k[i] = global_load_b64(kp);
-        st.v[i] = global_load_b64(vb + (int64_t)kr * p.v8_ss + slot * 8);
+        st.v[i] = global_load_b64(vb + (int64_t)kr * p.v_ss + slot * 8);
         st.ks[i] = global_load_f32(ksb + (int64_t)kr * p.ks_ss);
         st.vs[i] = global_load_f32(vsb + (int64_t)kr * p.vs_ss);
         st.ok[i] = global_load_u8(kvb ? kvb + kr : kp);
@@ -115,7 +109,7 @@ LWM_KERNEL(kFwdThreads) void attn_prefill_kv8_kernel(Kv8PrefillParams pp) {
     const int tid = thread_idx();
     const int wave = tid >> 6, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
 
-    // ---- block -> (q tile, head, batch, split): as attn_fwd_body<true>
+    // ---- block -> (q tile, head, batch, split): as attn_fwd_body
     const int nqt = (p.Sq + kFwdBQ - 1) / kFwdBQ;
     const int HB = p.H * p.B;
     const int nsplit = p.k_splits > 1 ? p.k_splits : 1;
@@ -132,8 +126,8 @@ LWM_KERNEL(kFwdThreads) void attn_prefill_kv8_kernel(Kv8PrefillParams pp) {
     const int b = hb / p.H, h = hb % p.H;
 
     const bf16_t* qb = p.q + (int64_t)b * p.q_sb + (int64_t)h * p.q_sh;
-    const uint8_t* kb = pp.k8 + (int64_t)b * pp.k8_sb + (int64_t)h * pp.k8_sh;
-    const uint8_t* vb = pp.v8 + (int64_t)b * pp.v8_sb + (int64_t)h * pp.v8_sh;
+    const uint8_t* kb = pp.k + (int64_t)b * pp.k_sb + (int64_t)h * pp.k_sh;
+    const uint8_t* vb = pp.v + (int64_t)b * pp.v_sb + (int64_t)h * pp.v_sh;
     const float* ksb = pp.k_scale + (int64_t)b * pp.ks_sb + h;
     const float* vsb = pp.v_scale + (int64_t)b * pp.vs_sb + h;
     const uint8_t* kvb = p.key_valid ? p.key_valid + (int64_t)b * pp.kv_sb : nullptr;
@@ -188,7 +182,6 @@ LWM_KERNEL(kFwdThreads) void attn_prefill_kv8_kernel(Kv8PrefillParams pp) {
         nkt = nkt < s1 ? nkt : s1;
     }
 
-    ProfAcc pa = {};
     float m_run = -INFINITY;  // running max of raw scores (q.k, unscaled)
     float l_run = 0.0f;       // this half-wave's partial row sum
     f32x16 acc[4];
@@ -204,13 +197,13 @@ LWM_KERNEL(kFwdThreads) void attn_prefill_kv8_kernel(Kv8PrefillParams pp) {
         for (int kt = kt0; kt < nkt; kt += 2) {
             const bool more1 = kt + 1 < nkt;
             if (more1) fwd8_stage_load(pp, kb, vb, ksb, vsb, kvb, kt + 1, tid, stg);
-            fwd_tile<0, true>(p, cx, qf, kt, m_run, l_run, acc, pa);
+            fwd_tile<0>(p, cx, qf, kt, m_run, l_run, acc);
             if (more1) fwd8_stage_write<1>(cx, stg, kt + 1, p.Sk, has_valid);
             block_sync();
             if (!more1) break;
             const bool more2 = kt + 2 < nkt;
             if (more2) fwd8_stage_load(pp, kb, vb, ksb, vsb, kvb, kt + 2, tid, stg);
-            fwd_tile<1, true>(p, cx, qf, kt + 1, m_run, l_run, acc, pa);
+            fwd_tile<1>(p, cx, qf, kt + 1, m_run, l_run, acc);
             if (more2) fwd8_stage_write<0>(cx, stg, kt + 2, p.Sk, has_valid);
             block_sync();
         }

@@ -2,7 +2,7 @@
 // batch sizes past the GEMV's four rows (gemv.h feeds x through v_readlane into `rows` FMAs per weight element: right
 // for 1-4 rows, VALU-bound by 16).  Still weight streaming: W is read once, 2*K*N bytes (K*N as e4m3 bytes), for at
 // most 32 tokens.  Requires wave_ops.h + attn_bwd64.h (the host form of the 16x16x32 MFMA) + gemv.h (GemvParams, the K
-// partition, gemv_reduce_kernel) + gemv_w8.h (GemvW8Params) + attn_decode_kv8.h (cvt_e4m3x2_lo/hi) + attn_prefill_kv8.h
+// partition, gemv_reduce_kernel) + gemv_w8.h (GemvW8Params) + attn_decode_kv8.h (cvt_e4m3x2_lo/hi) + attn_decode.h
 // (global_load_b64).
 //
 // Work split: the GEMV's along K -- a workgroup owns kGemvKT = 128 rows of K of one matrix and writes f32 partials

@@ -1,7 +1,7 @@
 // gemv_w4.h -- 4-bit (OCP MXFP4: e2m1 codes, one e8m0 scale per 32 rows of K) decode weights: the quantiser and the weight
 // format of the GEMV that streams them.  Requires wave_ops.h + gemv.h (GemvParams, gemv_body, gemv_by_rows,
-// gemv_reduce_kernel) + attn_decode.h (unpack_bf16x8, f32x2, fma2) + attn_decode_kv4.h (cvt_e2m1x2, e8m0_to_f32,
-// Kv4Format: encode, kExpDrop, kMantTop) + attn_prefill_kv8.h (global_load_b64).
+// gemv_reduce_kernel) + attn_decode.h (unpack_bf16x8, f32x2, fma2, global_load_b64) + attn_decode_kv4.h (cvt_e2m1x2,
+// e8m0_to_f32, Kv4Format: encode, kExpDrop, kMantTop).
 //
 // Why: gemv_w8.h halved the bytes a cached-decode step streams; this pack halves them again.  Per (K, N) kernel it holds
 // K * N / 2 bytes of codes and one scale byte per 32 rows of K and column: 4.25 bits per weight, 0.266 of the bf16 bytes.

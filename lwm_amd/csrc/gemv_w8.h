@@ -1,6 +1,6 @@
 // gemv_w8.h -- 8-bit (OCP e4m3fn) decode weights: the quantiser and the weight format of the GEMV that streams them.
 // Requires wave_ops.h + gemv.h (GemvParams, gemv_body, gemv_by_rows, gemv_reduce_kernel) + attn_decode.h (unpack_bf16x8,
-// f32x2, fma2) + attn_decode_kv8.h (cvt_e4m3x2_lo/hi, pack_e4m3x4) + attn_prefill_kv8.h (global_load_b64).
+// f32x2, fma2, global_load_b64) + attn_decode_kv8.h (cvt_e4m3x2_lo/hi, pack_e4m3x4).
 //
 // Why: the projections of a cached-decode step stream every weight once per token (gemv.h); the bf16 kernel is
 // HBM-bound, so the lever left is the number of bytes.  Per (K, N) kernel the pack holds K * N e4m3 bytes and one f32

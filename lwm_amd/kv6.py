@@ -2,14 +2,12 @@
 lwm_attn_prefill_kv6 (include/lwm_hip.h "6-bit KV cache", csrc/attn_decode_kv6.h, csrc/attn_prefill_kv6.h).  As everything
 in lwm_amd.ops: hand-written HIP kernels on the current torch stream, no PyTorch / CPU fallback.  kv6_dequant alone is a
 torch expression: the yardstick of the tests."""
-import ctypes as C
-import math
-
 import torch
 
 from . import _capi
-from ._lib import lib
-from .ops import KvFormat, _kvq_attn_decode, _kvq_cache_write, _kvq_cache_write_at, _stream_ptr, _t4
+from ._lib import lib  # noqa: F401  (unused here: every call goes through ops.lib.  Kept as an attribute only because
+#                                      tests/test_kv6_boundary.py assigns to it; drop it with that assignment)
+from .ops import KvFormat, _kvq_attn_decode, _kvq_attn_prefill, _kvq_cache_write, _kvq_cache_write_at
 
 # magnitude code c = 0..31: c / 8 below 8, (1 + (c & 7) / 8) * 2^((c >> 3) - 1) from 8 on; bit 5 is the sign
 E2M3_VALUES = tuple(sign * (c / 8.0 if c < 8 else (1.0 + (c & 7) / 8.0) * 2.0 ** ((c >> 3) - 1)) for sign in (1.0, -1.0) for c in range(32))
@@ -66,53 +64,5 @@ def attn_prefill_kv6(q, cached_key, key_scale, cached_value, value_scale, *, q_s
     visible to query i iff j <= q_start + i and key_valid[b, j] != 0.  The blocks are dequantised on their way into LDS; no
     bf16 copy of the cache is made.  Returns normalised partials (o_parts f32 [k_splits,B,Sq,H,D], lse_parts f32
     [k_splits,B,H,Sq]) -- merge with ops.attn_combine."""
-    if not torch.is_tensor(q) or q.dim() != 4:
-        raise ValueError("attn_prefill_kv6: q: expected a bf16 (B,Sq,H,D) device tensor")
-    B, Sq, H, D = q.shape
-    if q.dtype != torch.bfloat16:
-        raise ValueError("attn_prefill_kv6: expected a bf16 (B,Sq,H,D) query (the 6-bit cache holds quantised bf16 rows; "
-                         "there is no float32 flavour)")
-    if Sq < 1 or D != 128:
-        raise ValueError(f"attn_prefill_kv6: q of shape {tuple(q.shape)}: need Sq >= 1 and head_dim 128")
-    a = _capi.LwmKv6PrefillArgs()
-    a.q = _t4(q, "q", torch.bfloat16)
-    if not torch.is_tensor(cached_key) or cached_key.dim() != 4:
-        raise ValueError(f"cached_key: expected a uint8 device tensor of shape ({B},Sk,{H},96)")
-    Sk = cached_key.shape[1]
-    if Sk < 1:
-        raise ValueError("cached_key: expected at least one cache row")
-    for n, c, s in (("key", cached_key, key_scale), ("value", cached_value, value_scale)):
-        if not torch.is_tensor(c) or not c.is_cuda or c.device != q.device or c.dtype != torch.uint8 or \
-                tuple(c.shape) != (B, Sk, H, 96) or c.stride(3) != 1:
-            raise ValueError(f"cached_{n}: expected a uint8 tensor of shape {(B, Sk, H, 96)} on {q.device} with contiguous bytes")
-        if not torch.is_tensor(s) or not s.is_cuda or s.device != q.device or s.dtype != torch.uint8 or \
-                tuple(s.shape) != (B, Sk, H, 4) or tuple(s.stride()[2:]) != (4, 1):
-            raise ValueError(f"{n}_scale: expected a uint8 tensor of shape {(B, Sk, H, 4)} on {q.device} with contiguous heads")
-    q_start = int(q_start)
-    if q_start < 0:
-        raise ValueError(f"attn_prefill_kv6: q_start = {q_start} < 0")
-    a.k, a.v = cached_key.data_ptr(), cached_value.data_ptr()
-    a.k_stride_b, a.k_stride_s, a.k_stride_h = cached_key.stride()[:3]
-    a.v_stride_b, a.v_stride_s, a.v_stride_h = cached_value.stride()[:3]
-    a.k_scale, a.v_scale = key_scale.data_ptr(), value_scale.data_ptr()
-    a.k_scale_stride_b, a.k_scale_stride_s = key_scale.stride()[:2]
-    a.v_scale_stride_b, a.v_scale_stride_s = value_scale.stride()[:2]
-    if key_valid is not None:
-        m = key_valid
-        if not torch.is_tensor(m) or not m.is_cuda or m.device != q.device or m.dtype != torch.uint8 or \
-                tuple(m.shape) != (B, Sk) or m.stride(1) != 1:
-            raise ValueError(f"key_valid: expected a u8 tensor of shape {(B, Sk)} on {q.device} with contiguous keys")
-        a.key_valid, a.key_valid_stride_b = m.data_ptr(), m.stride(0)
-    a.B, a.Sq, a.Sk, a.H, a.D = B, Sq, Sk, H, D
-    a.q_start = q_start
-    a.scale = float(scale) if scale is not None else 1.0 / math.sqrt(D)
-    k_splits = max(1, int(k_splits))
-    if k_splits > 4096:
-        raise ValueError(f"attn_prefill_kv6: k_splits = {k_splits} > 4096")
-    a.k_splits = k_splits
-    o_parts = torch.empty((k_splits, B, Sq, H, D), dtype=torch.float32, device=q.device)
-    lse_parts = torch.empty((k_splits, B, H, Sq), dtype=torch.float32, device=q.device)
-    a.out_acc, a.lse_acc = o_parts.data_ptr(), lse_parts.data_ptr()
-    L = lib()
-    _capi.check(L, L.lwm_attn_prefill_kv6(C.byref(a), _stream_ptr()), "lwm_attn_prefill_kv6")
-    return o_parts, lse_parts
+    return _kvq_attn_prefill(KV6, "lwm_attn_prefill_kv6", _capi.LwmKv6PrefillArgs, q, cached_key, key_scale, cached_value,
+                             value_scale, q_start=q_start, k_splits=k_splits, key_valid=key_valid, scale=scale)

@@ -396,6 +396,65 @@ def _kvq_attn_decode(f, q, cached_key, key_scale, cached_value, value_scale, *, 
     return o_parts, lse_parts
 
 
+def _kvq_attn_prefill(f, entry, args, q, cached_key, key_scale, cached_value, value_scale, *, q_start, k_splits, key_valid=None,
+                      scale=None):
+    """A block of queries over format f's cache through the C entry point `entry`, whose argument struct is `args`
+    (kv8.attn_prefill_kv8 and kv6.attn_prefill_kv6 have the contract)."""
+    who = f"attn_prefill_{f.name}"
+    if not torch.is_tensor(q) or q.dim() != 4:
+        raise ValueError(f"{who}: q: expected a bf16 (B,Sq,H,D) device tensor")
+    B, Sq, H, D = q.shape
+    if q.dtype != torch.bfloat16:
+        raise ValueError(f"{who}: expected a bf16 (B,Sq,H,D) query (the {f.bits} cache holds quantised bf16 rows; there is no "
+                         "float32 flavour)")
+    if Sq < 1 or D != 128:
+        raise ValueError(f"{who}: q of shape {tuple(q.shape)}: need Sq >= 1 and head_dim 128")
+    a = args()
+    a.q = _t4(q, "q", torch.bfloat16)
+    if not torch.is_tensor(cached_key) or cached_key.dim() != 4:
+        raise ValueError(f"cached_key: expected a uint8 device tensor of shape ({B},Sk,{H},{f.head_bytes})")
+    Sk = cached_key.shape[1]
+    if Sk < 1:
+        raise ValueError("cached_key: expected at least one cache row")
+    cshape, sshape = (B, Sk, H, f.head_bytes), (B, Sk, H) + f.scale_tail
+    sstride = (math.prod(f.scale_tail),) + (1,) * len(f.scale_tail)         # the scales of a head and the heads of a row contiguous
+    for n, c, s in (("key", cached_key, key_scale), ("value", cached_value, value_scale)):
+        if not torch.is_tensor(c) or not c.is_cuda or c.device != q.device or c.dtype != torch.uint8 or \
+                tuple(c.shape) != cshape or c.stride(3) != 1:
+            raise ValueError(f"cached_{n}: expected a uint8 tensor of shape {cshape} on {q.device} with contiguous bytes")
+        if not torch.is_tensor(s) or not s.is_cuda or s.device != q.device or s.dtype != f.scale_dtype or \
+                tuple(s.shape) != sshape or tuple(s.stride()[2:]) != sstride:
+            raise ValueError(f"{n}_scale: expected a {f.scale_dtype} tensor of shape {sshape} on {q.device} with contiguous heads")
+    q_start = int(q_start)
+    if q_start < 0:
+        raise ValueError(f"{who}: q_start = {q_start} < 0")
+    a.k, a.v = cached_key.data_ptr(), cached_value.data_ptr()
+    a.k_stride_b, a.k_stride_s, a.k_stride_h = cached_key.stride()[:3]
+    a.v_stride_b, a.v_stride_s, a.v_stride_h = cached_value.stride()[:3]
+    a.k_scale, a.v_scale = key_scale.data_ptr(), value_scale.data_ptr()
+    a.k_scale_stride_b, a.k_scale_stride_s = key_scale.stride()[:2]
+    a.v_scale_stride_b, a.v_scale_stride_s = value_scale.stride()[:2]
+    if key_valid is not None:
+        m = key_valid
+        if not torch.is_tensor(m) or not m.is_cuda or m.device != q.device or m.dtype != torch.uint8 or \
+                tuple(m.shape) != (B, Sk) or m.stride(1) != 1:
+            raise ValueError(f"key_valid: expected a u8 tensor of shape {(B, Sk)} on {q.device} with contiguous keys")
+        a.key_valid, a.key_valid_stride_b = m.data_ptr(), m.stride(0)
+    a.B, a.Sq, a.Sk, a.H, a.D = B, Sq, Sk, H, D
+    a.q_start = q_start
+    a.scale = float(scale) if scale is not None else 1.0 / math.sqrt(D)
+    k_splits = max(1, int(k_splits))
+    if k_splits > 4096:
+        raise ValueError(f"{who}: k_splits = {k_splits} > 4096")
+    a.k_splits = k_splits
+    o_parts = torch.empty((k_splits, B, Sq, H, D), dtype=torch.float32, device=q.device)
+    lse_parts = torch.empty((k_splits, B, H, Sq), dtype=torch.float32, device=q.device)
+    a.out_acc, a.lse_acc = o_parts.data_ptr(), lse_parts.data_ptr()
+    L = lib()
+    _capi.check(L, getattr(L, entry)(C.byref(a), _stream_ptr()), entry)
+    return o_parts, lse_parts
+
+
 def kv8_cache_write(cache, scale, src, *, dst_row0, src_row0=0, nrows=None):
     """Quantise src[:, src_row0:src_row0+nrows] (bf16) into the 8-bit cache at row dst_row0: `cache` takes the e4m3fn
     bytes, `scale` one power-of-two f32 per (row, head) (lwm_kv8_cache_write; the format: include/lwm_hip.h)."""
