@@ -754,6 +754,53 @@ typedef struct LwmGemvW4Args {
 } LwmGemvW4Args;
 int lwm_gemv_fused_w4(const LwmGemvW4Args* args, void* stream);
 
+/* ------------------------------------------------------------------ 6-bit decode weights (lwm_version() >= 640)
+ * OCP MXFP6 (e2m3) copies of the same kernels, between the two above: 6.25 bits per weight, 0.391 of the bf16 bytes and
+ * 0.757 of the 8-bit pack's, with e4m3's three mantissa bits.  A bf16 kernel W of shape [K, N] (K % 32 == 0, K <= 12288,
+ * N % 8 == 0) becomes
+ *   q      uint8 [K/4][N/8][24]       e2m3 codes (sign in bit 5, exponent with bias 1 in bits 4-3, mantissa in bits 2-0:
+ *                                     magnitude code c = 0..31 is c / 8 below 8 and (1 + (c & 7) / 8) * 2^((c >> 3) - 1) from
+ *                                     8 on, 7.5 at most), 3 K N / 4 bytes.  NOT row-major: slot [k4][n8] holds rows
+ *                                     4 k4 .. 4 k4 + 3 of columns 8 n8 .. 8 n8 + 7 as 32 codes, code 8 j + c being row
+ *                                     4 k4 + j, column 8 n8 + c; code i sits at bits [6 i, 6 i + 6) of the slot's 24 bytes
+ *                                     read as one little-endian 192-bit integer (the block convention of the 6-bit KV
+ *                                     cache).  W[k][n] is therefore code i = 8 (k & 3) + (n & 7) of the slot at byte
+ *                                     ((k >> 2) * (N / 8) + (n >> 3)) * 24.  A slot is 8-byte aligned, not 16-byte aligned;
+ *                                     one slot of a GEMV lane brings four rows of its eight columns, and the 64 lanes of a
+ *                                     wave read 1536 contiguous bytes;
+ *   scale  uint8 [K/32][N]            one e8m0 byte b per MX block -- 32 consecutive rows of K of one column, the rows one
+ *                                     wave of the GEMV walks: the scale 2^(b - 127).
+ * Quantising one block: the rule of the 4-bit weights with 7.5 in place of 6 (that of the 6-bit KV cache).  amax = max |w|
+ * over the block; s = the smallest power of two with amax / s <= 7.5, its exponent byte clamped to [1, 254], and byte 127
+ * when amax == 0; q = e2m3(w / s), round to nearest, ties to the even code.  w / s is exact and |w / s| <= 7.5: nothing
+ * saturates; -0 keeps its sign.  Non-finite weights (Inf, NaN) are NOT supported, nor is a block whose amax reaches
+ * 1.9375 * 2^127 (its largest element would round up to 2^128, past the top of bf16).
+ * lwm_w6_quantise: one pass over w [K, N] bf16 -> q, scale_e8m0 and `rounded` [K, N] bf16 = bf16(e2m3(q) * s), the value
+ *   the codes stand for (`rounded` may be w itself: rounding in place).  Every pointer 16-byte aligned.  No atomics: the
+ *   same input gives the same bits.
+ * lwm_gemv_fused_w6: lwm_gemv_fused_bf16 with w[i] = the codes and w_scale[i] = the scale bytes of kernel i; every other
+ *   field means what it means in LwmGemvArgs (rows <= 4, K % 32 == 0, K <= 12288; N[i] % 8 == 0; workspace of the sum of
+ *   lwm_gemv_workspace_bytes(rows, K, N[i]) bytes), and the refusals are those of lwm_gemv_fused_w8 and lwm_gemv_fused_w4.
+ *   Same K partition, same order of every sum as the bf16 entry; the block's scale multiplies the sum over the block's 32
+ *   rows once.
+ * lwm_gemm_rows_fused_w6 (declared with the other 1..32-row entries below): lwm_gemm_rows_fused_bf16 over the same packs,
+ *   the codes becoming the rounded bf16 values e2m3(q) * s on their way to the matrix instruction; refusals as
+ *   lwm_gemm_rows_fused_w8.
+ * Exactness domain: e2m3(q) * s has 4 significant bits and is a bf16 value whenever it is a normal number, and with
+ *   power-of-two scales and neither overflow nor underflow in the partial sums (scales between 2^-40 and 2^40 and
+ *   activations of ordinary size are well inside) the results -- outputs and workspace partials -- are BIT FOR BIT those
+ *   of lwm_gemv_fused_bf16 (lwm_gemm_rows_fused_bf16 for the rows entry) on the `rounded` weights. */
+int lwm_w6_quantise(const void* w, void* q, void* scale_e8m0, void* rounded, int32_t K, int32_t N, void* stream);
+typedef struct LwmGemvW6Args {
+    const void* x; int64_t ldx; int32_t nmat; int32_t rows, K;
+    const void* w[3]; const uint8_t* w_scale[3]; void* y[3]; int64_t ldy[3]; float* y_f32[3]; int32_t N[3];
+    void* workspace;
+    const void* norm_weight; const float* ss_in; int32_t ss_n; float eps;
+    const void* residual[3]; int64_t ldres[3];
+    float* ss_out;
+} LwmGemvW6Args;
+int lwm_gemv_fused_w6(const LwmGemvW6Args* args, void* stream);
+
 /* ------------------------------------------------------------------ decode projections for 1..32 rows (lwm_version() >= 560)
  * The same products on the matrix pipe (v_mfma_f32_16x16x32_bf16) for batches past the GEMV's four rows: W is still read
  * once.  Every field of LwmGemvArgs / LwmGemvW8Args means what it means for lwm_gemv_fused_bf16 / lwm_gemv_fused_w8, with
@@ -781,6 +828,7 @@ int lwm_gemv_fused_w4(const LwmGemvW4Args* args, void* stream);
 int64_t lwm_gemm_rows_workspace_bytes(int32_t rows, int32_t K, int32_t N);
 int lwm_gemm_rows_fused_bf16(const LwmGemvArgs* args, void* stream);     /* rows 1..32 */
 int lwm_gemm_rows_fused_w8(const LwmGemvW8Args* args, void* stream);
+int lwm_gemm_rows_fused_w6(const LwmGemvW6Args* args, void* stream);     /* lwm_version() >= 640 */
 
 /* tux.cross_entropy_loss_and_accuracy as used at lwm/train.py:177-181, :192-201, per row of
  * bf16 logits [rows, V] (V % 8 == 0, V <= 32768): nll[r] = logsumexp(row) - row[target[r]] in
@@ -1011,7 +1059,7 @@ int lwm_version(void);
  * sizeof(LwmSampleArgs) (4) / sizeof(LwmKv8DecodeArgs) (5) / sizeof(LwmKv8PrefillArgs) (6) / sizeof(LwmAdamWArgs) (7) as
  * sizeof(LwmAdamWTensor) (8: an element of a device table that the caller lays out) / sizeof(LwmGemvW8Args) (9) /
  * sizeof(LwmKv4DecodeArgs) (10) / sizeof(LwmGemvW4Args) (11) / sizeof(LwmFramesArgs) (12) /
- * sizeof(LwmKv6DecodeArgs) (13) / sizeof(LwmKv6PrefillArgs) (14) as compiled into the library:
+ * sizeof(LwmKv6DecodeArgs) (13) / sizeof(LwmKv6PrefillArgs) (14) / sizeof(LwmGemvW6Args) (15) as compiled into the library:
  * lets a foreign-language binding verify its struct mirror at load time. */
 int lwm_sizeof(int which);
 

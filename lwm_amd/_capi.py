@@ -104,6 +104,11 @@ class LwmGemvW4Args(C.Structure):
     _fields_ = LwmGemvW8Args._fields_
 
 
+class LwmGemvW6Args(C.Structure):
+    """LwmGemvArgs with w[i] as 24-byte slots of e2m3 codes plus their e8m0 scale-byte tables"""
+    _fields_ = LwmGemvW8Args._fields_
+
+
 class LwmKv8DecodeArgs(C.Structure):
     _fields_ = [
         ("q", LwmTensor4), ("k", C.c_void_p), ("v", C.c_void_p),
@@ -298,9 +303,12 @@ PROTOTYPES = {
     "lwm_gemv_fused_w8": (C.c_int, [C.POINTER(LwmGemvW8Args), C.c_void_p]),
     "lwm_w4_quantise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "lwm_gemv_fused_w4": (C.c_int, [C.POINTER(LwmGemvW4Args), C.c_void_p]),
+    "lwm_w6_quantise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "lwm_gemv_fused_w6": (C.c_int, [C.POINTER(LwmGemvW6Args), C.c_void_p]),
     "lwm_gemm_rows_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "lwm_gemm_rows_fused_bf16": (C.c_int, [C.POINTER(LwmGemvArgs), C.c_void_p]),
     "lwm_gemm_rows_fused_w8": (C.c_int, [C.POINTER(LwmGemvW8Args), C.c_void_p]),
+    "lwm_gemm_rows_fused_w6": (C.c_int, [C.POINTER(LwmGemvW6Args), C.c_void_p]),
     "lwm_sample_tokens": (C.c_int, [C.POINTER(LwmSampleArgs), C.c_void_p]),
     "lwm_adamw_grad_norm": (C.c_int, [C.POINTER(LwmAdamWArgs), C.c_void_p]),
     "lwm_adamw_step": (C.c_int, [C.POINTER(LwmAdamWArgs), C.c_void_p]),
@@ -333,7 +341,7 @@ def bind(lib):
     for which, cls in ((0, LwmAttnArgs), (1, LwmConvArgs), (2, LwmRingArgs), (4, LwmSampleArgs), (5, LwmKv8DecodeArgs),
                        (6, LwmKv8PrefillArgs), (7, LwmAdamWArgs), (8, LwmAdamWTensor), (9, LwmGemvW8Args),
                        (10, LwmKv4DecodeArgs), (11, LwmGemvW4Args), (12, LwmFramesArgs), (13, LwmKv6DecodeArgs),
-                       (14, LwmKv6PrefillArgs)):
+                       (14, LwmKv6PrefillArgs), (15, LwmGemvW6Args)):
         if lib.lwm_sizeof(which) != C.sizeof(cls):
             raise ImportError(f"{cls.__name__}: ctypes mirror is {C.sizeof(cls)} bytes, library has "
                               f"{lib.lwm_sizeof(which)} (include/lwm_hip.h and lwm_amd/_capi.py out of step)")

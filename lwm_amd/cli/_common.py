@@ -77,10 +77,15 @@ def apply_decode_weights(model):
     keep 8-bit packs of them for the one-token steps (model.quantize_decode_weights: 0.516 of the weight bytes per token,
     +0.516x weight memory; bf16 models on one rank).  LWM_DECODE_WEIGHTS=fp4: the same with MXFP4 packs (0.266 of the bytes,
     +0.266x weight memory; 4-bit rounding moves the logits -- check quality on the model in use).  'bf16' or unset: nothing
-    happens."""
+    happens.  LWM_DECODE_WEIGHTS=fp6: MXFP6 (e2m3) packs between the two (0.391 of the bytes, +0.391x weight memory; three
+    mantissa bits, as e4m3; one-token steps of up to decode_rows rows stream them)."""
     mode = os.environ.get("LWM_DECODE_WEIGHTS", "").lower()
-    if mode not in ("", "bf16", "fp8", "fp4"):
-        raise SystemExit(f"LWM_DECODE_WEIGHTS={mode!r}: 'fp8', 'bf16' (the default), 'fp4' or unset")
+    if mode not in ("", "bf16", "fp8", "fp6", "fp4"):
+        raise SystemExit(f"LWM_DECODE_WEIGHTS={mode!r}: 'fp8', 'bf16' (the default), 'fp6', 'fp4' or unset")
+    if mode == "fp6":
+        model.quantize_decode_weights("fp6")
+        note("LWM_DECODE_WEIGHTS=fp6: projection kernels rounded in place to MXFP6 (e2m3) values; one-token steps stream the "
+             "6-bit packs")
     if mode == "fp4":
         model.quantize_decode_weights("fp4")
         note("LWM_DECODE_WEIGHTS=fp4: projection kernels rounded in place to MXFP4 values; one-token steps of up to 4 rows stream "

@@ -13,6 +13,7 @@
 #include "attn_prefill_kv6.h"
 #include "gemv_w8.h"
 #include "gemv_w4.h"
+#include "gemv_w6.h"
 #include "gemm_rows.h"
 
 namespace lwm {
@@ -761,7 +762,7 @@ int64_t lwm_gemv_workspace_bytes(int32_t rows, int32_t K, int32_t N) {
 
 }  // extern "C"
 namespace lwm {
-// The five fused projection entries (gemv.h, gemv_w8.h, gemv_w4.h, gemm_rows.h) share their checks, the K partition of GemvParams and
+// The seven fused projection entries (gemv.h, gemv_w8.h, gemv_w4.h, gemv_w6.h, gemm_rows.h) share their checks, the K partition of GemvParams and
 // the launch pair with gemv_reduce_kernel.  What differs per entry is written down here.
 struct ProjEntry {
     const char* tag;           // opens every text of lwm_last_error()
@@ -779,17 +780,18 @@ struct ProjEntry {
 static const void* const* proj_scales(const LwmGemvArgs*) { return nullptr; }
 static const void* const* proj_scales(const LwmGemvW8Args* a) { return (const void* const*)a->w_scale; }
 static const void* const* proj_scales(const LwmGemvW4Args* a) { return (const void* const*)a->w_scale; }
+static const void* const* proj_scales(const LwmGemvW6Args* a) { return (const void* const*)a->w_scale; }
 static const GemvParams& proj_params(void (*)(GemvParams), const GemvW8Params& pp) { return pp.g; }
 static const GemvW8Params& proj_params(void (*)(GemvW8Params), const GemvW8Params& pp) { return pp; }
-static GemvW4Params proj_params(void (*)(GemvW4Params), const GemvW8Params& pp) {      // (the same pointers, typed as bytes)
+static GemvW4Params proj_params(void (*)(GemvW4Params), const GemvW8Params& pp) {      // (the same pointers, typed as bytes; GemvW6Params too)
     GemvW4Params p4;
     p4.g = pp.g;
     for (int i = 0; i < kGemvMaxMats; ++i) { p4.q[i] = pp.q[i]; p4.scale[i] = (const uint8_t*)pp.scale[i]; }
     return p4;
 }
 
-// A = LwmGemvArgs with a kernel over GemvParams, or LwmGemvW8Args / LwmGemvW4Args with a kernel over GemvW8Params /
-// GemvW4Params (scale tables exist).
+// A = LwmGemvArgs with a kernel over GemvParams, or LwmGemvW8Args / LwmGemvW4Args / LwmGemvW6Args with a kernel over
+// GemvW8Params / GemvW4Params = GemvW6Params (scale tables exist).
 // The checks run in the order every entry has run them; the texts are format strings over the tag.
 template <class A, class P>
 static int proj_run(const ProjEntry& e, void (*kernel)(P), const A* a, void* stream) {
@@ -860,9 +862,13 @@ static const ProjEntry kProjGemvW8 = {"gemv_w8", "gemv_w8", kGemvMaxRows, true, 
                                       0, 3 * kGemvW8NT * 4};
 static const ProjEntry kProjGemvW4 = {"gemv_w4", "gemv_w4", kGemvMaxRows, true, kGemvNT, false, false, true, true,
                                       0, 3 * kGemvNT * 4};
+static const ProjEntry kProjGemvW6 = {"gemv_w6", "gemv_w6", kGemvMaxRows, true, kGemvNT, false, false, true, true,
+                                      0, 3 * kGemvNT * 4};
 static const ProjEntry kProjRows = {"gemm_rows", "gemm_rows_bf16", kRowsMax, false, kRowsNT, true, true, false, true,
                                     kRowsLdsBytes, 0};
 static const ProjEntry kProjRowsW8 = {"gemm_rows_w8", "gemm_rows_w8", kRowsMax, false, kRowsNT, true, true, false, true,
+                                      kRowsLdsBytes, 0};
+static const ProjEntry kProjRowsW6 = {"gemm_rows_w6", "gemm_rows_w6", kRowsMax, false, kRowsNT, true, true, false, true,
                                       kRowsLdsBytes, 0};
 }  // namespace lwm
 extern "C" {
@@ -925,12 +931,30 @@ int lwm_w4_quantise(const void* w, void* q, void* scale_e8m0, void* rounded, int
 
 int lwm_gemv_fused_w4(const LwmGemvW4Args* a, void* stream) { return lwm::proj_run(lwm::kProjGemvW4, lwm::gemv_w4_kernel, a, stream); }
 
+int lwm_w6_quantise(const void* w, void* q, void* scale_e8m0, void* rounded, int32_t K, int32_t N, void* stream) {
+    using namespace lwm;
+    if (!w || !q || !scale_e8m0 || !rounded) return fail(LWM_EINVAL, "%s", "w6_quantise: null pointer");
+    if (K <= 0 || N <= 0) return fail(LWM_EINVAL, "%s", "w6_quantise: bad dimension");
+    if ((K & 31) || K > 8 * 12 * kGemvKT || (N & 7))
+        return fail(LWM_EUNSUPPORTED, "%s: K=%ld N=%ld (need K %% 32 == 0, K <= 12288, N %% 8 == 0)", "w6_quantise", K, N);
+    if (!aligned16(w) || !aligned16(q) || !aligned16(scale_e8m0) || !aligned16(rounded))
+        return fail(LWM_EINVAL, "%s", "w6_quantise: misaligned pointer");
+    W6QuantParams p;
+    p.w = (const bf16_t*)w; p.q = (uint8_t*)q; p.scale = (uint8_t*)scale_e8m0; p.rounded = (bf16_t*)rounded; p.K = K; p.N = N;
+    const long grid = (long)((K + kGemvKT - 1) / kGemvKT) * ((N + kW4QuantNT - 1) / kW4QuantNT);
+    return launch("w6_quantise", w6_quantise_kernel, grid, 256, 0, stream, p);
+}
+
+int lwm_gemv_fused_w6(const LwmGemvW6Args* a, void* stream) { return lwm::proj_run(lwm::kProjGemvW6, lwm::gemv_w6_kernel, a, stream); }
+
 // 1..32 rows on the matrix pipe (gemm_rows.h)
 int64_t lwm_gemm_rows_workspace_bytes(int32_t rows, int32_t K, int32_t N) { return lwm_gemv_workspace_bytes(rows, K, N); }
 
 int lwm_gemm_rows_fused_bf16(const LwmGemvArgs* a, void* stream) { return lwm::proj_run(lwm::kProjRows, lwm::gemm_rows_bf16_kernel, a, stream); }
 
 int lwm_gemm_rows_fused_w8(const LwmGemvW8Args* a, void* stream) { return lwm::proj_run(lwm::kProjRowsW8, lwm::gemm_rows_w8_kernel, a, stream); }
+
+int lwm_gemm_rows_fused_w6(const LwmGemvW6Args* a, void* stream) { return lwm::proj_run(lwm::kProjRowsW6, lwm::gemm_rows_w6_kernel, a, stream); }
 
 int lwm_softmax_ce_bf16(const void* logits, const int32_t* target, const float* weight, float* nll,
                         int32_t* correct, void* dlogits, int64_t rows, int32_t V, void* stream) {
@@ -1038,9 +1062,9 @@ int lwm_adamw_step(const LwmAdamWArgs* a, void* stream) {
 int lwm_adamw_chunk(void) { return lwm::kAdamWChunk; }
 
 const char* lwm_last_error(void) { return lwm::g_err; }
-int lwm_version(void) { return 630; }
+int lwm_version(void) { return 640; }
 int lwm_sizeof(int which) {
-    return which == 0 ? (int)sizeof(LwmAttnArgs) : which == 1 ? (int)sizeof(LwmConvArgs) : which == 2 ? (int)sizeof(LwmRingArgs) : which == 3 ? (int)sizeof(LwmGemvArgs) : which == 4 ? (int)sizeof(LwmSampleArgs) : which == 5 ? (int)sizeof(LwmKv8DecodeArgs) : which == 6 ? (int)sizeof(LwmKv8PrefillArgs) : which == 7 ? (int)sizeof(LwmAdamWArgs) : which == 8 ? (int)sizeof(LwmAdamWTensor) : which == 9 ? (int)sizeof(LwmGemvW8Args) : which == 10 ? (int)sizeof(LwmKv4DecodeArgs) : which == 11 ? (int)sizeof(LwmGemvW4Args) : which == 12 ? (int)sizeof(LwmFramesArgs) : which == 13 ? (int)sizeof(LwmKv6DecodeArgs) : which == 14 ? (int)sizeof(LwmKv6PrefillArgs) : -1;
+    return which == 0 ? (int)sizeof(LwmAttnArgs) : which == 1 ? (int)sizeof(LwmConvArgs) : which == 2 ? (int)sizeof(LwmRingArgs) : which == 3 ? (int)sizeof(LwmGemvArgs) : which == 4 ? (int)sizeof(LwmSampleArgs) : which == 5 ? (int)sizeof(LwmKv8DecodeArgs) : which == 6 ? (int)sizeof(LwmKv8PrefillArgs) : which == 7 ? (int)sizeof(LwmAdamWArgs) : which == 8 ? (int)sizeof(LwmAdamWTensor) : which == 9 ? (int)sizeof(LwmGemvW8Args) : which == 10 ? (int)sizeof(LwmKv4DecodeArgs) : which == 11 ? (int)sizeof(LwmGemvW4Args) : which == 12 ? (int)sizeof(LwmFramesArgs) : which == 13 ? (int)sizeof(LwmKv6DecodeArgs) : which == 14 ? (int)sizeof(LwmKv6PrefillArgs) : which == 15 ? (int)sizeof(LwmGemvW6Args) : -1;
 }
 
 }  // extern "C"

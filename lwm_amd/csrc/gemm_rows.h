@@ -2,7 +2,7 @@
 // batch sizes past the GEMV's four rows (gemv.h feeds x through v_readlane into `rows` FMAs per weight element: right
 // for 1-4 rows, VALU-bound by 16).  Still weight streaming: W is read once, 2*K*N bytes (K*N as e4m3 bytes), for at
 // most 32 tokens.  Requires wave_ops.h + attn_bwd64.h (the host form of the 16x16x32 MFMA) + gemv.h (GemvParams, the K
-// partition, gemv_reduce_kernel) + gemv_w8.h (GemvW8Params) + attn_decode_kv8.h (cvt_e4m3x2_lo/hi) + attn_decode.h
+// partition, gemv_reduce_kernel) + gemv_w8.h (GemvW8Params) + gemv_w6.h (GemvW6Params, GemvW6Format::offset) + attn_decode_kv8.h (cvt_e4m3x2_lo/hi) + attn_decode.h
 // (global_load_b64).
 //
 // Work split: the GEMV's along K -- a workgroup owns kGemvKT = 128 rows of K of one matrix and writes f32 partials
@@ -27,7 +27,11 @@
 //     functions gave the same bits and registers but cost the 32-row tile 1-3 % with the norm on (profiles/r16_proj_refactor.md);
 //   * 8-bit packs (gemv_w8.h's format): the bytes become bf16 on their way into LDS (an e4m3 value is exact in bf16), the
 //     group's power-of-two scale multiplies the finished partial once; everything between is the bf16 kernel's
-//     instruction stream.
+//     instruction stream;
+//   * 6-bit packs (gemv_w6.h's format): a lane takes four 24-byte slots (four rows of its eight columns each, one MX block
+//     of the group per slot) and writes each as four rows of the rounded bf16 values e2m3(q) * s -- the tile image is bit for
+//     bit the bf16 kernel's on the rounded weights, and everything after the LDS write is its instruction stream.  (A
+//     ds_write_b128 lane group now writes half of eight rows, not two whole ones: bank conflicts cost time, not bits.)
 // Row independence: output (r, n) is one dot product of the MFMA, fed by x[r] and column n alone; neither `rows`, nor the
 // row's slot in the tile, nor its neighbours enter it.
 // x must be 16-byte aligned with ldx % 8 == 0 (the GEMV reads x by the element and does not care).
@@ -58,9 +62,31 @@ LWM_DEVICE u32x4 rows_e4m3x8_to_bf16(u32x2 w) {
     return u32x4{pack_bf16x2(a[0], a[1]), pack_bf16x2(b[0], b[1]), pack_bf16x2(c[0], c[1]), pack_bf16x2(d[0], d[1])};
 }
 
-// RB = row blocks of 16 (1: rows <= 16, 2: rows <= 32); W8: q / scale hold the matrices (else p.w)
-template <int RB, bool W8>
-LWM_DEVICE void gemm_rows_body(const GemvParams& p, const uint8_t* const* q, const float* const* scale) {
+// The weight format of the body: bf16 kernels (p.w), or the packs of gemv_w8.h / gemv_w6.h (q / scale hold the matrices)
+enum RowsFormat { kRowsBf16, kRowsW8, kRowsW6 };
+
+// One slot of a 6-bit pack (four rows of eight columns, gemv_w6.h) -> the four rows as the rounded bf16 values
+// e2m3(q) * s, s = the eight column scales of the slot's MX block (e8m0 bytes): exact, so the tile image is the bf16
+// kernel's on the rounded weights.
+LWM_DEVICE void rows_e2m3x32_to_bf16(u32x6 w, u32x2 sb, u32x4 (&o)[4]) {
+    f32x2 c[16], s[4];
+    cvt_e2m3x32_f32(w, c);
+    for (int h = 0; h < 4; ++h) {
+        const uint32_t two = sb[h >> 1] >> (16 * (h & 1));
+        s[h] = f32x2{e8m0_to_f32(two & 255u), e8m0_to_f32((two >> 8) & 255u)};
+    }
+    for (int j = 0; j < 4; ++j)
+        for (int h = 0; h < 4; ++h) {
+            const f32x2 v = c[4 * j + h] * s[h];
+            o[j][h] = pack_bf16x2(v[0], v[1]);
+        }
+}
+
+// RB = row blocks of 16 (1: rows <= 16, 2: rows <= 32); F: the weight format; S: its scale type (f32 per 128 rows of K
+// for kRowsW8, e8m0 bytes per 32 rows for kRowsW6)
+template <int RB, RowsFormat F, class S>
+LWM_DEVICE void gemm_rows_body(const GemvParams& p, const uint8_t* const* q, const S* const* scale) {
+    constexpr bool W8 = F == kRowsW8, W6 = F == kRowsW6;
     const int tid = thread_idx();
     const int wave = wave_uniform(tid >> 6), lane = tid & 63;
     int mi = 0;                                    // which matrix this workgroup belongs to (uniform)
@@ -84,12 +110,27 @@ LWM_DEVICE void gemm_rows_body(const GemvParams& p, const uint8_t* const* q, con
     nc = nc < N ? nc : N - 8;
     u32x4 wv[16];
     u32x2 wq[16];
+    u32x6 w6[4];
+    u32x2 s6[4];
+    if constexpr (W6) {
+        // 6-bit packs: four slots per lane.  Slot u: k4 = 8u + (lane >> 3) of the group, n8 = lane & 7 of the wave's 64
+        // columns -- rows 32u + 4 (lane >> 3) .. + 3, inside MX block u of the group, whose eight column scales ride along.
 #pragma unroll
-    for (int u = 0; u < 16; ++u) {
-        const int k = k0 + 8 * u + lr;
-        const int64_t at = (int64_t)(k < p.K ? k : p.K - 1) * N + nc;
-        if constexpr (W8) wq[u] = global_load_b64(q[mi] + at);
-        else wv[u] = global_load_b128(p.w[mi] + at);
+        for (int u = 0; u < 4; ++u) {
+            const int k = k0 + 32 * u + 4 * lr;
+            const uint8_t* at = q[mi] + GemvW6Format::offset(k < p.K ? k : p.K - 4, nc, N);
+            const u32x2 a = global_load_b64(at), b = global_load_b64(at + 8), c = global_load_b64(at + 16);
+            w6[u] = u32x6{a[0], a[1], b[0], b[1], c[0], c[1]};
+            s6[u] = global_load_b64(scale[mi] + (int64_t)((k < p.K ? k : p.K - 4) >> 5) * N + nc);
+        }
+    } else {
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {
+            const int k = k0 + 8 * u + lr;
+            const int64_t at = (int64_t)(k < p.K ? k : p.K - 1) * N + nc;
+            if constexpr (W8) wq[u] = global_load_b64(q[mi] + at);
+            else wv[u] = global_load_b128(p.w[mi] + at);
+        }
     }
 
     // ---- x: fragment (rb, s) = batch row 16 rb + (lane & 15), k = k0 + 32 s + 8 (lane >> 4) .. + 7
@@ -135,10 +176,20 @@ LWM_DEVICE void gemm_rows_body(const GemvParams& p, const uint8_t* const* q, con
     }
 
     // ---- W into the wave's tile image
+    if constexpr (W6) {
 #pragma unroll
-    for (int u = 0; u < 16; ++u) {
-        if constexpr (W8) wv[u] = rows_e4m3x8_to_bf16(wq[u]);
-        lds_write_b128(lds + rows_off(8 * u + lr, c8 * 2), wv[u]);
+        for (int u = 0; u < 4; ++u) {
+            u32x4 o[4];
+            rows_e2m3x32_to_bf16(w6[u], s6[u], o);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) lds_write_b128(lds + rows_off(32 * u + 4 * lr + j, c8 * 2), o[j]);
+        }
+    } else {
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {
+            if constexpr (W8) wv[u] = rows_e4m3x8_to_bf16(wq[u]);
+            lds_write_b128(lds + rows_off(8 * u + lr, c8 * 2), wv[u]);
+        }
     }
     wave_lds_fence();
 
@@ -185,13 +236,18 @@ LWM_DEVICE void gemm_rows_body(const GemvParams& p, const uint8_t* const* q, con
 
 // dynamic LDS: kRowsLdsBytes
 LWM_KERNEL(kRowsThreads) void gemm_rows_bf16_kernel(GemvParams p) {
-    if (p.R <= 16) gemm_rows_body<1, false>(p, nullptr, nullptr);       // (uniform)
-    else gemm_rows_body<2, false>(p, nullptr, nullptr);
+    if (p.R <= 16) gemm_rows_body<1, kRowsBf16, float>(p, nullptr, nullptr);       // (uniform)
+    else gemm_rows_body<2, kRowsBf16, float>(p, nullptr, nullptr);
 }
 
 LWM_KERNEL(kRowsThreads) void gemm_rows_w8_kernel(GemvW8Params pp) {
-    if (pp.g.R <= 16) gemm_rows_body<1, true>(pp.g, pp.q, pp.scale);
-    else gemm_rows_body<2, true>(pp.g, pp.q, pp.scale);
+    if (pp.g.R <= 16) gemm_rows_body<1, kRowsW8>(pp.g, pp.q, pp.scale);
+    else gemm_rows_body<2, kRowsW8>(pp.g, pp.q, pp.scale);
+}
+
+LWM_KERNEL(kRowsThreads) void gemm_rows_w6_kernel(GemvW6Params pp) {
+    if (pp.g.R <= 16) gemm_rows_body<1, kRowsW6>(pp.g, pp.q, pp.scale);
+    else gemm_rows_body<2, kRowsW6>(pp.g, pp.q, pp.scale);
 }
 
 }  // namespace lwm

@@ -385,6 +385,7 @@ class LLaMAForCausalLM(torch.nn.Module):
         self._freqs = None
         self._w8 = None            # quantize_decode_weights("fp8"): {parameter name: lwm_amd.w8.W8Kernel}
         self._w4 = None            # quantize_decode_weights("fp4"): {parameter name: lwm_amd.w4.W4Kernel}; _w8 stays None
+        self._w6 = None            # quantize_decode_weights("fp6"): {parameter name: lwm_amd.w6.W6Kernel}; one kind at a time
         self._decode_rows = None   # decode_rows: None = LWM_DECODE_ROWS
         self._remat_blocks = None  # remat_blocks: None = LWM_REMAT_BLOCK
 
@@ -423,7 +424,7 @@ class LLaMAForCausalLM(torch.nn.Module):
     @property
     def decode_rows(self):
         """None, or N in 5..32: cached one-token steps of up to N batch rows run through the fused step and
-        lwm_gemm_rows_fused_bf16 / _w8 (csrc/gemm_rows.h) instead of block by block through the library GEMMs, and the
+        lwm_gemm_rows_fused_bf16 / _w8 / _w6 (csrc/gemm_rows.h) instead of block by block through the library GEMMs, and the
         heads' f32 logits with them.  Opt-in (such steps then differ in their low bits); unset, the attribute reads
         LWM_DECODE_ROWS.  Values outside 5..32 raise ValueError."""
         return parse_decode_rows(os.environ.get("LWM_DECODE_ROWS")) if self._decode_rows is None else self._decode_rows
@@ -518,14 +519,19 @@ class LLaMAForCausalLM(torch.nn.Module):
         body for more than 4 rows: where decode_rows is set, steps of 5.. rows run lwm_gemm_rows_fused_bf16 over the bf16
         parameters -- those ARE the rounded model, so that route computes the same model and only saves no bytes.  4-bit
         round-to-nearest moves a model's logits far more than the 8-bit packs do: check quality on the model in use.
-        A later "fp8" replaces the 4-bit packs (rounding the already rounded kernels again) and the other way round; only one
-        kind of pack is held at a time.
+        mode="fp6": the same with 6-bit packs (include/lwm_hip.h "6-bit decode weights", lwm_amd/w6.py): the kernels are ROUNDED
+        IN PLACE to their MXFP6 values (e2m3 codes -- three mantissa bits, as e4m3 -- and one power-of-two scale per 32 rows of K
+        and column); the fused one-token step and the heads' f32 logits stream the packs, lwm_gemv_fused_w6 at up to 4 rows and
+        lwm_gemm_rows_fused_w6 at 5..decode_rows rows -- bit for bit what the bf16 entries give on the rounded parameters, from
+        0.391 of the bytes (0.757 of the 8-bit packs'); the weights take 1.391x their memory.
+        A later "fp8" replaces the 4-bit or 6-bit packs (rounding the already rounded kernels again) and the other way round;
+        only one kind of pack is held at a time.
         bf16 models on one rank."""
         if mode in (None, "bf16"):
             return self.drop_decode_weights()
-        if mode not in ("fp8", "fp4"):
-            raise ValueError(f"quantize_decode_weights({mode!r}): 'fp8', 'fp4', or 'bf16' / None (drop_decode_weights)")
-        bits = "8-bit" if mode == "fp8" else "4-bit"
+        if mode not in ("fp8", "fp6", "fp4"):
+            raise ValueError(f"quantize_decode_weights({mode!r}): 'fp8', 'fp6', 'fp4', or 'bf16' / None (drop_decode_weights)")
+        bits = {"fp8": "8-bit", "fp6": "6-bit", "fp4": "4-bit"}[mode]
         if self.dtype != torch.bfloat16:
             raise NotImplementedError(f"quantize_decode_weights({mode!r}) with a float32 model: the {bits} packs are made from bf16 "
                                       "kernels and the GEMV that streams them takes bf16 activations (--dtype=bf16, or bf16 weights)")
@@ -534,6 +540,8 @@ class LLaMAForCausalLM(torch.nn.Module):
                                       "(one rank, or bf16 decode weights)")
         if mode == "fp8":
             from .w8 import quantise_weight
+        elif mode == "fp6":
+            from .w6 import quantise_weight
         else:
             from .w4 import quantise_weight
         packs = {}
@@ -542,12 +550,12 @@ class LLaMAForCausalLM(torch.nn.Module):
                 packs[name] = quantise_weight(p)
             except ValueError as e:
                 raise ValueError(f"quantize_decode_weights({mode!r}): {name}: {e}") from None
-        self._w8, self._w4 = (packs, None) if mode == "fp8" else (None, packs)
+        self._w8, self._w6, self._w4 = (packs if mode == m else None for m in ("fp8", "fp6", "fp4"))
         return self
 
     def drop_decode_weights(self):
         """Back to bf16 weight streaming.  The parameters stay as they are (rounded, if they were quantised)."""
-        self._w8 = self._w4 = None
+        self._w8 = self._w6 = self._w4 = None
         return self
 
     def _w8_packs(self, names, kernels):
@@ -557,6 +565,10 @@ class LLaMAForCausalLM(torch.nn.Module):
     def _w4_packs(self, names, kernels):
         """the same for the 4-bit packs"""
         return [self._w4[n].check(k, n) for n, k in zip(names, kernels)]
+
+    def _w6_packs(self, names, kernels):
+        """the same for the 6-bit packs"""
+        return [self._w6[n].check(k, n) for n, k in zip(names, kernels)]
 
     def _decode_layers_fused(self, x, fc, attention_mask, position_ids, cache):
         """The blocks of a cached one-token step (lwm/llama.py:704-744 with q_len = 1) with each RMSNorm folded into the
@@ -571,6 +583,11 @@ class LLaMAForCausalLM(torch.nn.Module):
             fused_w8 = w8.gemv_fused_w8 if B <= 4 else w8.gemm_rows_fused_w8
             names = {id(p): n for n, p in self._decode_weight_params()}
             gemv_fused = lambda x, ks, **kw: fused_w8(x, self._w8_packs([names[id(k)] for k in ks], ks), **kw)    # noqa: E731
+        elif getattr(self, "_w6", None) is not None:       # ... over the 6-bit packs, at every row count as the 8-bit ones
+            from . import w6
+            fused_w6 = w6.gemv_fused_w6 if B <= 4 else w6.gemm_rows_fused_w6
+            names = {id(p): n for n, p in self._decode_weight_params()}
+            gemv_fused = lambda x, ks, **kw: fused_w6(x, self._w6_packs([names[id(k)] for k in ks], ks), **kw)    # noqa: E731
         elif getattr(self, "_w4", None) is not None and B <= 4:    # ... over the 4-bit packs (above 4 rows: the rounded bf16 parameters)
             from . import w4
             names = {id(p): n for n, p in self._decode_weight_params()}
@@ -739,11 +756,12 @@ class LLaMAForCausalLM(torch.nn.Module):
         return chunked_lm_head_loss(h, self.lm_head, target_tokens, loss_masks, chunk, sp_sharded=sp_sharded)
 
 
-def w8_head_logits(model, h, head):
+def w8_head_logits(model, h, head, kind="w8"):
     """f32 logits of a head through its 8-bit pack (quantize_decode_weights), where the model has one for `head` and the
-    rows go through the GEMV (at most four, no autograd); None otherwise -- the caller then runs
-    `dense(h, head, torch.float32)` as before (a stand-in model without packs always gets None)"""
-    packs = getattr(model, "_w8", None)
+    rows go through the GEMV (at most four, no autograd) or, up to decode_rows, the rows entry; None otherwise -- the caller
+    then runs `dense(h, head, torch.float32)` as before (a stand-in model without packs always gets None).  kind="w6": the
+    same over the 6-bit packs (w6_head_logits)"""
+    packs = getattr(model, "_" + kind, None)
     if packs is None:
         return None
     same = lambda p: p is head or (p.data_ptr() == head.data_ptr() and p.shape == head.shape and p.stride() == head.stride())
@@ -752,13 +770,19 @@ def w8_head_logits(model, h, head):
     limit = max(4, model_decode_rows(model) or 4)
     if name is None or rows > limit or not h.is_cuda or h.dtype != torch.bfloat16 or torch.is_grad_enabled():
         return None
-    from . import w8
+    import importlib
+    mod = importlib.import_module("." + kind, __package__)          # (looked up at call time: the entries can be wrapped)
     h2 = h.reshape(rows, h.shape[-1])
     if rows > 4 and not rows_x_ok(h2):
         h2 = h2.clone(memory_format=torch.contiguous_format)
-    fused = w8.gemv_fused_w8 if rows <= 4 else w8.gemm_rows_fused_w8
-    (y,) = fused(h2, model._w8_packs((name,), (head,)), out_dtype=torch.float32)
+    fused = getattr(mod, "gemv_fused_" + kind if rows <= 4 else "gemm_rows_fused_" + kind)
+    (y,) = fused(h2, getattr(model, f"_{kind}_packs")((name,), (head,)), out_dtype=torch.float32)
     return y.reshape(*h.shape[:-1], y.shape[-1])
+
+
+def w6_head_logits(model, h, head):
+    """w8_head_logits for the 6-bit packs: the GEMV at up to four rows, lwm_gemm_rows_fused_w6 up to decode_rows"""
+    return w8_head_logits(model, h, head, "w6")
 
 
 def w4_head_logits(model, h, head):
@@ -785,9 +809,11 @@ def model_decode_rows(model):
 
 
 def head_logits(model, h, head):
-    """f32 logits of `head`: through its 8-bit or 4-bit pack where the model has one, else `dense(h, head, torch.float32)`
+    """f32 logits of `head`: through its 8-bit, 6-bit or 4-bit pack where the model has one, else `dense(h, head, torch.float32)`
     (the GEMV for <= 4 rows, lwm_gemm_rows_fused_bf16 up to model.decode_rows, the library beyond)"""
     y = w8_head_logits(model, h, head)
+    if y is None:
+        y = w6_head_logits(model, h, head)
     if y is None:
         y = w4_head_logits(model, h, head)
     if y is not None:

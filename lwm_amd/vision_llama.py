@@ -26,7 +26,7 @@ class VideoLLaMAConfig(LLaMAConfig):
 
 
 def _head_logits(model, h, head):
-    """`dense(h, head, torch.float32)`, through the head's 8-bit pack where the model has one (llama.head_logits)"""
+    """`dense(h, head, torch.float32)`, through the head's 8-bit, 6-bit or 4-bit pack where the model has one (llama.head_logits)"""
     return head_logits(model, h, head)
 
 
@@ -58,7 +58,7 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
         x = self._embed(input_ids, vision_masks)
         if self.decode_rows is not None:
             # opt-in (decode_rows / LWM_DECODE_ROWS): a cached one-token step of sample_mode 'text' / 'vision' takes the
-            # fused step of the text model at any row count the option covers -- and with it the 8-bit packs
+            # fused step of the text model at any row count the option covers -- and with it the 8-bit or 6-bit packs
             return self._layers(x, n_sp, attention_mask, segment_ids, position_ids, cache, layout)
         return self.ln_f(self._blocks(x, self._table(x.device), attention_mask, segment_ids, position_ids, cache, layout))
 
