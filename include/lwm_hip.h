@@ -952,6 +952,51 @@ int lwm_adamw_step(const LwmAdamWArgs* args, void* stream);
 /* elements of one chunk of the chunk table (a constant of the library) */
 int lwm_adamw_chunk(void);
 
+/* ------------------------------------------------------------------ dropout (lwm_version() >= 650)
+ * Residual and embedding dropout of the training step (lwm/llama.py:423 / :618, :656-660, :998 / :1017) over contiguous
+ * [B,S,C] tensors, bf16 or f32, C % 8 == 0, every pointer 16-byte aligned:
+ *
+ *   lwm_dropout_add_*:  y[b,s,c] = round( res[b,s,c] + (keep ? x[b,s,c] * inv : +0) )        res NULL: round(keep ? x * inv : +0)
+ *   lwm_dropout_bwd_*:  y[b,s,c] = round( keep ? x[b,s,c] * inv : +0 )                       x = the gradient of y above,
+ *                       y = the gradient of x; `res` is not read -- the gradient of res is the incoming gradient itself.
+ *
+ *   x * inv is ONE f32 product rounded to f32 and the add ONE f32 addition (never a fused multiply-add); `round` is one
+ *   round-to-nearest-even to bf16, and nothing for f32.  A dropped element adds exactly +0.  y may alias x or res.
+ *
+ * The keep mask is a function of the arguments alone -- nothing is stored, nothing has state -- so the backward, a
+ * recompute of the forward and a call on the rows [s0, s1) of a tensor with s_offset = s0 see the bits the whole
+ * forward saw.  THE RULE: one Philox4x32-10 call (the generator of the token sampler: the round constants and key
+ * schedule of rocRAND's philox4x32_10 engine) serves the 8 channels [8v, 8v + 8) of a row,
+ *     key     = (key0, key1)
+ *     counter = (c / 8, s_offset + s, b, site)                               (32-bit words; s_offset + S <= 2^32)
+ *     h(c)    = 16 bits of output word (c % 8) / 2: its LOW half for even c, its HIGH half for odd c
+ *     drop    iff h(c) < thr16
+ * with thr16 an integer in [0, 65535] that the CALLER computes as round(p * 65536).  The drop probability is therefore
+ * EXACTLY thr16 / 65536, not p: p = 0.1 gives thr16 = 6554 and drops 6554 / 65536 = 0.100006... of the elements.  `inv`
+ * is the f32 nearest to 1 / (1 - thr16 / 65536), computed by the caller in f64.  thr16 = 0 drops nothing (with inv = 1:
+ * the plain rounded sum); thr16 = 65535 keeps an element with probability 2^-16.  `site` tells the call sites of one step
+ * apart (lwm_amd/llama.py: 0 the embedding, 1 + 2 i / 2 + 2 i the attention / MLP output of layer i); (key0, key1) is the
+ * caller's (seed, step).  The masks are this library's own stream of i.i.d. bits; they are NOT the bits jax's threefry
+ * generator gives the reference for the same seed.
+ *
+ * LWM_EINVAL, checked in this order: x or y NULL; a negative dimension (or s_offset < 0, s_offset + S > 2^32);
+ * C % 8 != 0; a misaligned pointer; thr16 > 65535; inv not finite or < 1.  B, S or C equal to 0: LWM_OK, nothing is
+ * launched. */
+typedef struct LwmDropoutArgs {
+    const void* x;             /* [B,S,C] */
+    const void* res;           /* [B,S,C] or NULL */
+    void* y;                   /* [B,S,C] */
+    int32_t B, S, C;
+    int64_t s_offset;          /* the row of the whole sequence that row 0 of these tensors is */
+    uint32_t site, key0, key1;
+    uint32_t thr16;
+    float inv;
+} LwmDropoutArgs;
+int lwm_dropout_add_bf16(const LwmDropoutArgs* args, void* stream);
+int lwm_dropout_add_f32(const LwmDropoutArgs* args, void* stream);
+int lwm_dropout_bwd_bf16(const LwmDropoutArgs* args, void* stream);
+int lwm_dropout_bwd_f32(const LwmDropoutArgs* args, void* stream);
+
 /* ------------------------------------------------------------------ VQGAN
  * Primitives of the video tokeniser, lwm/vqgan.py.  All tensors are f32, NHWC,
  * dense; results are bit-exact with oracle/vqgan_ref.c (exact-f32 MFMA, fixed
@@ -1059,7 +1104,8 @@ int lwm_version(void);
  * sizeof(LwmSampleArgs) (4) / sizeof(LwmKv8DecodeArgs) (5) / sizeof(LwmKv8PrefillArgs) (6) / sizeof(LwmAdamWArgs) (7) as
  * sizeof(LwmAdamWTensor) (8: an element of a device table that the caller lays out) / sizeof(LwmGemvW8Args) (9) /
  * sizeof(LwmKv4DecodeArgs) (10) / sizeof(LwmGemvW4Args) (11) / sizeof(LwmFramesArgs) (12) /
- * sizeof(LwmKv6DecodeArgs) (13) / sizeof(LwmKv6PrefillArgs) (14) / sizeof(LwmGemvW6Args) (15) as compiled into the library:
+ * sizeof(LwmKv6DecodeArgs) (13) / sizeof(LwmKv6PrefillArgs) (14) / sizeof(LwmGemvW6Args) (15) /
+ * sizeof(LwmDropoutArgs) (16) as compiled into the library:
  * lets a foreign-language binding verify its struct mirror at load time. */
 int lwm_sizeof(int which);
 

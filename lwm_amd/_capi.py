@@ -185,6 +185,12 @@ class LwmAdamWArgs(C.Structure):
     ]
 
 
+class LwmDropoutArgs(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("res", C.c_void_p), ("y", C.c_void_p), ("B", C.c_int32), ("S", C.c_int32), ("C", C.c_int32),
+                ("s_offset", C.c_int64), ("site", C.c_uint32), ("key0", C.c_uint32), ("key1", C.c_uint32), ("thr16", C.c_uint32),
+                ("inv", C.c_float)]
+
+
 RING_GROUP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
 RING_SEND_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p)
 
@@ -313,6 +319,10 @@ PROTOTYPES = {
     "lwm_adamw_grad_norm": (C.c_int, [C.POINTER(LwmAdamWArgs), C.c_void_p]),
     "lwm_adamw_step": (C.c_int, [C.POINTER(LwmAdamWArgs), C.c_void_p]),
     "lwm_adamw_chunk": (C.c_int, []),
+    "lwm_dropout_add_bf16": (C.c_int, [C.POINTER(LwmDropoutArgs), C.c_void_p]),
+    "lwm_dropout_add_f32": (C.c_int, [C.POINTER(LwmDropoutArgs), C.c_void_p]),
+    "lwm_dropout_bwd_bf16": (C.c_int, [C.POINTER(LwmDropoutArgs), C.c_void_p]),
+    "lwm_dropout_bwd_f32": (C.c_int, [C.POINTER(LwmDropoutArgs), C.c_void_p]),
     "lwm_cast_f32_to_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "lwm_sum_f32_to_bf16": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "lwm_conv2d_nhwc_f32": (C.c_int, [C.POINTER(LwmConvArgs), C.c_void_p]),
@@ -341,7 +351,7 @@ def bind(lib):
     for which, cls in ((0, LwmAttnArgs), (1, LwmConvArgs), (2, LwmRingArgs), (4, LwmSampleArgs), (5, LwmKv8DecodeArgs),
                        (6, LwmKv8PrefillArgs), (7, LwmAdamWArgs), (8, LwmAdamWTensor), (9, LwmGemvW8Args),
                        (10, LwmKv4DecodeArgs), (11, LwmGemvW4Args), (12, LwmFramesArgs), (13, LwmKv6DecodeArgs),
-                       (14, LwmKv6PrefillArgs), (15, LwmGemvW6Args)):
+                       (14, LwmKv6PrefillArgs), (15, LwmGemvW6Args), (16, LwmDropoutArgs)):
         if lib.lwm_sizeof(which) != C.sizeof(cls):
             raise ImportError(f"{cls.__name__}: ctypes mirror is {C.sizeof(cls)} bytes, library has "
                               f"{lib.lwm_sizeof(which)} (include/lwm_hip.h and lwm_amd/_capi.py out of step)")

@@ -22,7 +22,13 @@ reference's param_dtype=float32), four HIP launches for clipping + update, and `
 record (lwm/train.py:216-222).  It runs on the gradients as they are after the all-reduce and adds no communication.
 
 --lwm_remat_block (off by default) sets model.remat_blocks: per-block activation recompute (lwm_amd/remat.py), the same
-loss and gradients from about an eighth of the kept activations; LWM_REMAT_BLOCK=1 does the same without the flag."""
+loss and gradients from about an eighth of the kept activations; LWM_REMAT_BLOCK=1 does the same without the flag.
+
+Dropout (--update_llama_config='dict(resid_pdrop=0.1,embd_pdrop=0.1)', the reference's deterministic=False step,
+lwm/train.py:174): where either rate is > 0, every micro-step names its random stream with
+model.set_dropout_rng(--seed, step * accumulate_gradient_steps + micro-step) -- the same --seed gives the same masks run
+after run, with or without --lwm_remat_block / --lwm_fused_optimizer.  The masks are this build's own Philox stream, not
+jax's; attn_pdrop > 0 and dropout on an sp axis > 1 are refused by name (lwm_amd/llama.py DropoutState)."""
 from __future__ import annotations
 
 import math
@@ -97,6 +103,10 @@ def main(argv=None):
     clip = float(opt_cfg.get("clip_gradient", 1.0))
     adamw = dict(lr=lr_at(0, opt_cfg), betas=(float(opt_cfg.get("b1", 0.9)), float(opt_cfg.get("b2", 0.95))),
                  weight_decay=float(opt_cfg.get("weight_decay", 1e-4)))
+    dropout = max(float(cfg.resid_pdrop), float(cfg.embd_pdrop)) > 0
+    if dropout:
+        C.note(f"dropout: resid_pdrop {cfg.resid_pdrop}, embd_pdrop {cfg.embd_pdrop}; masks from the Philox stream of "
+               f"(--seed {F.seed}, micro-step) -- lwm_amd.llama_ops.dropout_add")
     fused = bool(F.lwm_fused_optimizer)
     if fused:
         from ..optim import FusedAdamW
@@ -119,7 +129,9 @@ def main(argv=None):
         for pg in opt.param_groups:
             pg["lr"] = lr_at(step, opt_cfg)
         t0 = time.perf_counter()
-        for _ in range(accum):
+        for micro in range(accum):
+            if dropout:
+                model.set_dropout_rng(int(F.seed), step * accum + micro)
             # a global batch of seq+1 tokens; this process holds ITS rows of every sequence (sp_shard: the ownership
             # rule bound to the "sp" axis).  Each rank's loss is its share of the per-sequence mean (the count of targets
             # is summed over the ring inside the loss operator), so the shares add up to the 1-process loss.

@@ -5,6 +5,7 @@
 // misc_kernels.h and "lwm_hip.h" already included.
 #include "sample.h"
 #include "optim.h"
+#include "dropout.h"
 #include "attn_decode_kvq.h"
 #include "attn_decode_kv8.h"
 #include "attn_decode_kv4.h"
@@ -1061,10 +1062,54 @@ int lwm_adamw_step(const LwmAdamWArgs* a, void* stream) {
 
 int lwm_adamw_chunk(void) { return lwm::kAdamWChunk; }
 
+// ---------------------------------------------------------------- dropout (dropout.h)
+// the checks of the four entries, in the order include/lwm_hip.h lists them; -> the kernel's parameters
+static int dropout_params(const char* name, const LwmDropoutArgs* a, bool with_res, lwm::DropoutParams* p) {
+    using namespace lwm;
+    if (!a) return fail(LWM_EINVAL, "%s: args is null", name);
+    if (!a->x || !a->y) return fail(LWM_EINVAL, "%s: x or y is null", name);
+    if (a->B < 0 || a->S < 0 || a->C < 0) return fail(LWM_EINVAL, "%s: negative dimension", name);
+    if (a->s_offset < 0 || a->s_offset + a->S > ((int64_t)1 << 32))
+        return fail(LWM_EINVAL, "%s: s_offset = %ld (need 0 <= s_offset and s_offset + S <= 2^32: a counter word)", name, (long)a->s_offset);
+    if (a->C & 7) return fail(LWM_EINVAL, "%s: C = %ld is not a multiple of 8", name, (long)a->C);
+    if (!aligned16(a->x) || !aligned16(a->y) || (with_res && !aligned16(a->res))) return fail(LWM_EINVAL, "%s: misaligned pointer", name);
+    if (a->thr16 > 65535u) return fail(LWM_EINVAL, "%s: thr16 = %ld (at most 65535)", name, (long)a->thr16);
+    if (!isfinite(a->inv) || !(a->inv >= 1.0f)) return fail(LWM_EINVAL, "%s: inv must be finite and >= 1", name);
+    p->x = a->x; p->res = with_res ? a->res : nullptr; p->y = a->y;
+    p->nvec = (int64_t)a->B * a->S * (a->C / 8);
+    p->S = (uint32_t)a->S; p->Cv = (uint32_t)(a->C / 8);
+    p->s_offset = (uint32_t)a->s_offset; p->site = a->site; p->key0 = a->key0; p->key1 = a->key1;
+    p->thr16 = a->thr16; p->inv = a->inv;
+    return 0;
+}
+
+static int dropout_launch(const char* name, const LwmDropoutArgs* a, bool f32, bool with_res, void* stream) {
+    using namespace lwm;
+    DropoutParams p;
+    int r;
+    if ((r = dropout_params(name, a, with_res, &p))) return r;
+    if (p.nvec == 0) return LWM_OK;
+    // a bounded grid of 256-vector tiles, 8 blocks per compute unit; the blocks stride over the rest
+    const int64_t tiles = (p.nvec + 255) / 256, cap = 8 * device_cu_count();
+    const long blocks = (long)(tiles < cap ? tiles : cap);
+    if (f32) {
+        if (p.res) return launch(name, dropout_kernel<true, true>, blocks, 256, 0, stream, p);
+        return launch(name, dropout_kernel<true, false>, blocks, 256, 0, stream, p);
+    }
+    if (p.res) return launch(name, dropout_kernel<false, true>, blocks, 256, 0, stream, p);
+    return launch(name, dropout_kernel<false, false>, blocks, 256, 0, stream, p);
+}
+
+int lwm_dropout_add_bf16(const LwmDropoutArgs* a, void* stream) { return dropout_launch("dropout_add_bf16", a, false, a && a->res, stream); }
+int lwm_dropout_add_f32(const LwmDropoutArgs* a, void* stream) { return dropout_launch("dropout_add_f32", a, true, a && a->res, stream); }
+// dx = dropout'(g): x = g, y = dx; `res` is not read (its gradient is g itself: no kernel)
+int lwm_dropout_bwd_bf16(const LwmDropoutArgs* a, void* stream) { return dropout_launch("dropout_bwd_bf16", a, false, false, stream); }
+int lwm_dropout_bwd_f32(const LwmDropoutArgs* a, void* stream) { return dropout_launch("dropout_bwd_f32", a, true, false, stream); }
+
 const char* lwm_last_error(void) { return lwm::g_err; }
-int lwm_version(void) { return 640; }
+int lwm_version(void) { return 650; }
 int lwm_sizeof(int which) {
-    return which == 0 ? (int)sizeof(LwmAttnArgs) : which == 1 ? (int)sizeof(LwmConvArgs) : which == 2 ? (int)sizeof(LwmRingArgs) : which == 3 ? (int)sizeof(LwmGemvArgs) : which == 4 ? (int)sizeof(LwmSampleArgs) : which == 5 ? (int)sizeof(LwmKv8DecodeArgs) : which == 6 ? (int)sizeof(LwmKv8PrefillArgs) : which == 7 ? (int)sizeof(LwmAdamWArgs) : which == 8 ? (int)sizeof(LwmAdamWTensor) : which == 9 ? (int)sizeof(LwmGemvW8Args) : which == 10 ? (int)sizeof(LwmKv4DecodeArgs) : which == 11 ? (int)sizeof(LwmGemvW4Args) : which == 12 ? (int)sizeof(LwmFramesArgs) : which == 13 ? (int)sizeof(LwmKv6DecodeArgs) : which == 14 ? (int)sizeof(LwmKv6PrefillArgs) : which == 15 ? (int)sizeof(LwmGemvW6Args) : -1;
+    return which == 0 ? (int)sizeof(LwmAttnArgs) : which == 1 ? (int)sizeof(LwmConvArgs) : which == 2 ? (int)sizeof(LwmRingArgs) : which == 3 ? (int)sizeof(LwmGemvArgs) : which == 4 ? (int)sizeof(LwmSampleArgs) : which == 5 ? (int)sizeof(LwmKv8DecodeArgs) : which == 6 ? (int)sizeof(LwmKv8PrefillArgs) : which == 7 ? (int)sizeof(LwmAdamWArgs) : which == 8 ? (int)sizeof(LwmAdamWTensor) : which == 9 ? (int)sizeof(LwmGemvW8Args) : which == 10 ? (int)sizeof(LwmKv4DecodeArgs) : which == 11 ? (int)sizeof(LwmGemvW4Args) : which == 12 ? (int)sizeof(LwmFramesArgs) : which == 13 ? (int)sizeof(LwmKv6DecodeArgs) : which == 14 ? (int)sizeof(LwmKv6PrefillArgs) : which == 15 ? (int)sizeof(LwmGemvW6Args) : which == 16 ? (int)sizeof(LwmDropoutArgs) : -1;
 }
 
 }  // extern "C"

@@ -9,6 +9,7 @@
 //
 // Expects wave_ops.h (the product's or the host emulation's) to be included first.
 #pragma once
+#include "philox.h"      // philox4x32_10: the generator, shared with dropout.h
 
 namespace lwm {
 
@@ -42,22 +43,6 @@ struct SampleParams {
     int64_t seq_ld;
     int32_t seq_cols;
 };
-
-// Philox4x32-10 (Salmon et al., SC'11): the round constants and key schedule of rocRAND's philox4x32_10_engine.
-LWM_HD void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-    for (int r = 0; r < 10; ++r) {
-        if (r) {
-            k0 += 0x9E3779B9u;
-            k1 += 0xBB67AE85u;
-        }
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-        c[0] = n0;
-        c[1] = (uint32_t)p1;
-        c[2] = n2;
-        c[3] = (uint32_t)p0;
-    }
-}
 
 // u = ((x >> 9) + 1/2) * 2^-23: 23 bits, so u is exact in f32 and lies in [2^-24, 1 - 2^-24] -- never 0 or 1.
 // g = -log(-log(u)) is then within [-2.82, 16.64].

@@ -16,7 +16,7 @@ import os
 
 import torch
 
-from . import kv4 as _kv4, kv6 as _kv6, ops as _ops, remat as _remat
+from . import kv4 as _kv4, kv6 as _kv6, dropout as _dropout, llama_ops as _lo, ops as _ops, remat as _remat
 from .llama_ops import (LLaMAMLP, RMSNorm, apply_rotary_emb, chunked_lm_head_loss, decode_rows_scope, dense, dense_fused,
                         dense_multi, fused_dense_ok, parse_decode_rows, precompute_freqs_cis, qkv_rope, rmsnorm_residual,
                         rows_x_ok, swiglu)
@@ -60,7 +60,9 @@ def parse_config_updates(text):
 
 
 class LLaMAConfig:
-    """lwm/llama.py:133-199: same field names and defaults (dropout fields are 0 and unused)."""
+    """lwm/llama.py:133-199: same field names and defaults.  resid_pdrop and embd_pdrop are honoured by a training-mode
+    forward (DropoutState below); attn_pdrop > 0 is refused there: the reference hands it to a package that is not part
+    of it."""
 
     def __init__(self, vocab_size=32000, hidden_size=4096, intermediate_size=11008, num_hidden_layers=32,
                  num_attention_heads=32, max_sequence_length=4096, rms_norm_eps=1e-6, initializer_range=0.02,
@@ -69,7 +71,7 @@ class LLaMAConfig:
                  scan_key_chunk_size=1024, scan_mlp_chunk_size=1024, scan_layers=True, param_scan_axis=0, mesh_dim=None,
                  theta=10000, **kwargs):
         # (every keyword and default of the reference's signature -- tests/test_golden.py holds them to the reference's own
-        # __init__; scan_layers / param_scan_axis describe the checkpoint layout, the *_pdrop fields are 0 and unused)
+        # __init__; scan_layers / param_scan_axis describe the checkpoint layout)
         self.vocab_size, self.hidden_size, self.intermediate_size = vocab_size, hidden_size, intermediate_size
         self.num_hidden_layers, self.num_attention_heads = num_hidden_layers, num_attention_heads
         self.max_sequence_length, self.rms_norm_eps = max_sequence_length, rms_norm_eps
@@ -135,6 +137,36 @@ class LLaMAConfig:
         return cls(**cfg)
 
 
+class DropoutState:
+    """What the dropout sites of one model share: the (seed, step) pair of set_dropout_rng.  A site -- 0 the embedding,
+    1 + 2 i the attention output of layer i, 2 + 2 i its MLP output (lwm/llama.py:998 / :1017, :423 / :618, :656-660) -- is
+    ACTIVE iff its module is in training mode, its rate (embd_pdrop / resid_pdrop) is > 0 and there is no KV cache; an
+    active site runs lwm_amd.llama_ops.dropout_add, whose mask is a function of (seed, step, site, row, channel) and of
+    nothing else: no hidden global generator, nothing stored.  The backward, the recompute of a remat block and of an
+    MLP chunk read the pair again: it stays as it is until the step's backward has run.  The masks are this build's own
+    stream (i.i.d. keep with probability 1 - round(p * 65536) / 65536), not jax's threefry bits: a run does not reproduce
+    the reference's masks, only their distribution."""
+
+    def __init__(self):
+        self.rng = None
+
+    def set(self, seed, step):
+        self.rng = (_dropout._u32(seed, "seed"), _dropout._u32(step, "step"))
+
+    def site(self, module, rate, cache, site):
+        """None (inactive), or the (p, rng, site) that dropout_add takes"""
+        if not (module.training and rate > 0 and cache is None):
+            return None
+        if self.rng is None:
+            raise ValueError(f"a training-mode forward with dropout rate {rate} needs its random stream named: call "
+                             "model.set_dropout_rng(seed, step) before every step (model.eval() turns dropout off)")
+        if sp_size_rank("sp")[0] > 1:
+            raise NotImplementedError(
+                f"dropout (rate {rate}) with sp > 1: the mask is a function of the GLOBAL row, and handing a rank's rows "
+                "their global rows (dropout_add's s_offset, per run of the layout) is not wired up; one rank, or rates 0")
+        return (rate, self.rng, site)
+
+
 def _multi_rank():
     """More than one rank along the bound "sp" axis (never the WORLD size: see set_sp_group)."""
     return sp_size_rank("sp")[0] > 1
@@ -197,6 +229,11 @@ class LLaMAAttention(torch.nn.Module):
         balanced ownership table, lwm_amd.ring.balanced_layout).
         residual (extension): the block's `x`, added to the result (lwm/llama.py:726) -- in the wo GEMM's epilogue."""
         B, S, d = x.shape
+        if self.training and cache is None and self.cfg.attn_pdrop > 0:
+            raise NotImplementedError(
+                f"attn_pdrop = {self.cfg.attn_pdrop} in a training-mode forward: the reference hands it to the ringattention "
+                "package (lwm/llama.py:553-566), which is not part of it -- its semantics cannot be pinned; attn_pdrop=0, "
+                "or model.eval()")
         split = lambda t: t.reshape(B, S, self.num_heads, self.head_dim)      # reshape, no transpose (:434-438)
         fused = cache is None and freqs_cis.is_cuda and fused_dense_ok(x, (self.wq, self.wk, self.wv, self.wo))
         if fused:
@@ -352,8 +389,17 @@ class LLaMABlock(torch.nn.Module):
         self.attention = LLaMAAttention(cfg, dtype)
         self.ffn_norm = RMSNorm(cfg.hidden_size, cfg.rms_norm_eps, dtype)
         self.feed_forward = LLaMAMLP(cfg.hidden_size, cfg.intermediate_size, dtype, cfg.initializer_range)
+        self.layer_index = 0               # the model numbers its blocks: the dropout sites of layer i are 1 + 2 i, 2 + 2 i
+        self._dropout = DropoutState()     # (the model shares ONE state among its blocks)
+
+    def set_dropout_rng(self, seed, step):
+        """a block on its own: see LLaMAForCausalLM.set_dropout_rng"""
+        self._dropout.set(seed, step)
 
     def forward(self, x, freqs_cis, attention_mask=None, segment_ids=None, position_ids=None, cache=None, layout=None):
+        drop_a = self._dropout.site(self, self.cfg.resid_pdrop, cache, 1 + 2 * self.layer_index)
+        if drop_a is not None:
+            return self._forward_dropout(x, freqs_cis, attention_mask, segment_ids, position_ids, layout, drop_a)
         if cache is None and x.is_cuda and x.dtype == torch.bfloat16:
             # training / uncached branch: `x` goes through each norm as (norm(x), x) so that the residual branch's gradient
             # is added inside the RMSNorm backward kernel, and each residual add rides in the epilogue of the GEMM before it
@@ -371,6 +417,28 @@ class LLaMABlock(torch.nn.Module):
             ff = self.feed_forward(h)
         return x + ff
 
+    def _forward_dropout(self, x, freqs_cis, attention_mask, segment_ids, position_ids, layout, drop_a):
+        """forward with the residual dropout sites active (training mode, resid_pdrop > 0, no cache): both branches of
+        forward, with wo and w2 run WITHOUT their residual epilogue and dropout_add doing the add in their place
+        (lwm/llama.py:618 + :726, :660 + :743); the rmsnorm_residual pairing stays.  In the chunked MLP the dropout sits
+        inside the chunk, as in the reference (:659-660), each chunk at its own row offset, and the add stays outside."""
+        drop_m = (drop_a[0], drop_a[1], drop_a[2] + 1)
+        fused = x.is_cuda and x.dtype == torch.bfloat16
+        if fused:
+            h, x = rmsnorm_residual(self.attention_norm, x)
+        else:
+            h = self.attention_norm(x)
+        a = self.attention(h, freqs_cis, attention_mask, segment_ids, position_ids, None, layout)
+        x = _lo.dropout_add(a.contiguous(), x.contiguous(), *drop_a)
+        if fused:
+            h, x = rmsnorm_residual(self.ffn_norm, x)
+        else:
+            h = self.ffn_norm(x)
+        if self.cfg.scan_mlp and h.shape[1] >= self.cfg.scan_mlp_chunk_size:      # (:728-734)
+            return x + blockwise_feedforward(lambda c, s0: self.feed_forward(c, dropout=drop_m, s_offset=s0), h,
+                                             self.cfg.scan_mlp_chunk_size, with_offset=True)
+        return self.feed_forward(h, residual=x.contiguous(), dropout=drop_m)
+
 
 class LLaMAForCausalLM(torch.nn.Module):
     """FlaxLLaMAModule + lm_head (lwm/llama.py:982-1106), loss of lwm/train.py:171-181."""
@@ -380,6 +448,9 @@ class LLaMAForCausalLM(torch.nn.Module):
         self.cfg, self.dtype = cfg, dtype
         self.wte = torch.nn.Parameter(torch.randn(cfg.vocab_size, cfg.hidden_size).mul_(cfg.initializer_range).to(dtype))
         self.h = torch.nn.ModuleList(LLaMABlock(cfg, dtype) for _ in range(cfg.num_hidden_layers))
+        self._dropout = DropoutState()
+        for i, blk in enumerate(self.h):
+            blk.layer_index, blk._dropout = i, self._dropout
         self.ln_f = RMSNorm(cfg.hidden_size, cfg.rms_norm_eps, dtype)
         self.lm_head = _dense(cfg.hidden_size, cfg.vocab_size, cfg.initializer_range, dtype)
         self._freqs = None
@@ -447,9 +518,23 @@ class LLaMAForCausalLM(torch.nn.Module):
     def remat_blocks(self, on):
         self._remat_blocks = None if on is None else _remat.parse_remat_block(on, "remat_blocks")
 
+    def set_dropout_rng(self, seed, step):
+        """Names the random stream of the NEXT training step's dropout sites (DropoutState): two integers in [0, 2^32),
+        the Philox key as they stand (ValueError otherwise).  The same pair gives the same masks -- in the forward, the
+        backward and every recompute; a training loop passes its seed and a step counter that never repeats
+        (lwm_amd.cli.train: step * accumulate_gradient_steps + micro-step).  A training-mode forward with a rate > 0 and
+        no pair set raises ValueError; with both rates 0, in eval() and with a KV cache nothing reads it."""
+        self._dropout.set(seed, step)
+        return self
+
+    def _embd_dropout(self, x, cache):
+        """the embedding's dropout site (site 0; lwm/llama.py:1017, lwm/vision_llama.py:313) over embedded tokens x"""
+        drop = self._dropout.site(self, self.cfg.embd_pdrop, cache, 0)
+        return x if drop is None else _lo.dropout_add(x.contiguous(), None, *drop)
+
     def hidden_states(self, input_ids, attention_mask=None, segment_ids=None, position_ids=None, cache=None, layout=None):
         n_sp, position_ids = self._ring_position_ids(input_ids, position_ids, cache, layout)
-        x = torch.nn.functional.embedding(input_ids.long(), self.wte)
+        x = self._embd_dropout(torch.nn.functional.embedding(input_ids.long(), self.wte), cache)
         return self._layers(x, n_sp, attention_mask, segment_ids, position_ids, cache, layout)
 
     def _layers(self, x, n_sp, attention_mask, segment_ids, position_ids, cache, layout):

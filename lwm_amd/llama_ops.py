@@ -20,6 +20,7 @@ import torch
 
 from . import _capi
 from ._lib import lib
+from .dropout import dropout_add, dropout_threshold  # noqa: F401  (the operator lives in lwm_amd/dropout.py)
 from .decode_rows import decode_rows_limit, decode_rows_scope, gemm_rows_fused, parse_decode_rows, rows_x_ok  # noqa: F401
 from .ops import _stream_ptr, _t4
 
@@ -867,13 +868,21 @@ class LLaMAMLP(torch.nn.Module):
         self.w1, self.w2, self.w3 = mk(hidden_size, intermediate_size), mk(intermediate_size, hidden_size), \
             mk(hidden_size, intermediate_size)
 
-    def forward(self, x, residual=None):
+    def forward(self, x, residual=None, dropout=None, s_offset=0):
         """residual (extension): added to the result (the block's `x + ff`, lwm/llama.py:743) -- in the w2 GEMM's epilogue
-        on the fused path."""
+        on the fused path.
+        dropout (extension): None, or (p, rng, site) of an ACTIVE dropout site (lwm/llama.py:656-660; the block decides):
+        w2 then runs without the epilogue and dropout_add does the add; s_offset = the row of the sequence that row 0 of x
+        is (a chunk of the blockwise MLP)."""
         if fused_dense_ok(x, (self.w1, self.w3)) and self.w2.dtype == torch.bfloat16 and self.w2.is_contiguous() and \
                 self.w1.shape[1] % 8 == 0:
             # w1 | w3 as one GEMM, the gate on the halves of its output, w2 with the residual as its epilogue
-            return dense_fused(swiglu_halves(dense_fused(x, (self.w1, self.w3))), (self.w2,), residual)
+            h = swiglu_halves(dense_fused(x, (self.w1, self.w3)))
+            if dropout is not None:
+                return dropout_add(dense_fused(h, (self.w2,)), residual, *dropout, s_offset=s_offset)
+            return dense_fused(h, (self.w2,), residual)
         gate, up = dense_multi(x, (self.w1, self.w3))
         out = dense(swiglu(gate.contiguous(), up.contiguous()), self.w2)
+        if dropout is not None:
+            return dropout_add(out.contiguous(), residual, *dropout, s_offset=s_offset)
         return out if residual is None else residual + out

@@ -232,23 +232,27 @@ def concatenate_to_cache(cached_key, cached_value, key, value, cache_index, axis
                         new_sharded=new_sharded)
 
 
-def blockwise_feedforward(module, x, chunk_size, pre_remat=True):
+def blockwise_feedforward(module, x, chunk_size, pre_remat=True, with_offset=False):
     """lwm/llama.py:729-734: apply a position-wise module over sequence chunks (identical result to
     module(x)).  `pre_remat` (the reference wraps the MLP in remat with policy nothing_saveable,
     lwm/llama.py:673-678): each chunk's activations inside `module` are recomputed in the backward
-    instead of stored -- at 1M tokens the two (S, 11008) SwiGLU intermediates are 44 GB per layer."""
+    instead of stored -- at 1M tokens the two (S, 11008) SwiGLU intermediates are 44 GB per layer.
+    `with_offset`: the module is called as module(chunk, s0), s0 the chunk's first row -- what is position-wise only
+    given the row (the MLP's dropout, whose mask is a function of the row: lwm_amd.llama_ops.dropout_add) gets in chunks
+    what it would get in one piece."""
     S = x.shape[1]
 
-    def run(c):
+    def run(c, s0=0):
+        f = (lambda t: module(t, s0)) if with_offset else module
         # (inside the recompute of a remat block -- lwm_amd/remat.py -- the chunks run plainly: the block is being
         #  recomputed already, and a checkpoint here would run the MLP a third time)
         if pre_remat and torch.is_grad_enabled() and c.requires_grad and not _remat.recomputing():
             from torch.utils.checkpoint import checkpoint
-            return checkpoint(module, c, use_reentrant=False)
-        return module(c)
+            return checkpoint(f, c, use_reentrant=False)
+        return f(c)
 
     if chunk_size is None or S <= chunk_size:
         return run(x)
     if S % chunk_size:
         raise ValueError(f"sequence length {S} is not a multiple of chunk_size {chunk_size}")
-    return torch.cat([run(c) for c in x.split(chunk_size, dim=1)], dim=1)
+    return torch.cat([run(c, i * chunk_size) for i, c in enumerate(x.split(chunk_size, dim=1))], dim=1)

@@ -55,7 +55,7 @@ class VideoLLaMAForCausalLM(LLaMAForCausalLM):
     def hidden_states(self, input_ids, vision_masks, attention_mask=None, segment_ids=None, position_ids=None,
                       cache=None, layout=None):
         n_sp, position_ids = self._ring_position_ids(input_ids, position_ids, cache, layout)
-        x = self._embed(input_ids, vision_masks)
+        x = self._embd_dropout(self._embed(input_ids, vision_masks), cache)      # (after the vte / wte mix: :313)
         if self.decode_rows is not None:
             # opt-in (decode_rows / LWM_DECODE_ROWS): a cached one-token step of sample_mode 'text' / 'vision' takes the
             # fused step of the text model at any row count the option covers -- and with it the 8-bit or 6-bit packs
