@@ -72,27 +72,28 @@ def sampler_kwargs(model, seed, generator):
     return dict(seed=seed, graph=graph, **extra)
 
 
+# what apply_decode_weights notes per LWM_DECODE_WEIGHTS mode (the modes: lwm_amd.wpack.FORMATS)
+_DECODE_WEIGHTS_NOTES = {
+    "fp8": "projection kernels rounded in place to e4m3 values; one-token steps stream the 8-bit packs",
+    "fp6": "projection kernels rounded in place to MXFP6 (e2m3) values; one-token steps stream the 6-bit packs",
+    "fp4": "projection kernels rounded in place to MXFP4 values; one-token steps of up to 4 rows stream the 4-bit packs",
+}
+
+
 def apply_decode_weights(model):
-    """LWM_DECODE_WEIGHTS=fp8: once the weights are loaded, round the projection kernels in place to their e4m3 values and
-    keep 8-bit packs of them for the one-token steps (model.quantize_decode_weights: 0.516 of the weight bytes per token,
-    +0.516x weight memory; bf16 models on one rank).  LWM_DECODE_WEIGHTS=fp4: the same with MXFP4 packs (0.266 of the bytes,
-    +0.266x weight memory; 4-bit rounding moves the logits -- check quality on the model in use).  'bf16' or unset: nothing
-    happens.  LWM_DECODE_WEIGHTS=fp6: MXFP6 (e2m3) packs between the two (0.391 of the bytes, +0.391x weight memory; three
-    mantissa bits, as e4m3; one-token steps of up to decode_rows rows stream them)."""
+    """LWM_DECODE_WEIGHTS=fp8 / fp6 / fp4: once the weights are loaded, round the projection kernels in place to the format's
+    values and keep packs of them for the one-token steps (model.quantize_decode_weights; bf16 models on one rank).  fp8:
+    e4m3, 0.516 of the weight bytes per token, +0.516x weight memory.  fp6: MXFP6 (e2m3: three mantissa bits, as e4m3),
+    0.391 of the bytes, +0.391x weight memory; as the 8-bit packs, streamed by one-token steps of up to decode_rows rows.
+    fp4: MXFP4, 0.266 of the bytes, +0.266x weight memory; 4-bit rounding moves the logits -- check quality on the model
+    in use.  'bf16' or unset: nothing happens."""
+    from ..wpack import FORMATS
     mode = os.environ.get("LWM_DECODE_WEIGHTS", "").lower()
-    if mode not in ("", "bf16", "fp8", "fp6", "fp4"):
+    if mode not in ("", "bf16", *FORMATS):
         raise SystemExit(f"LWM_DECODE_WEIGHTS={mode!r}: 'fp8', 'bf16' (the default), 'fp6', 'fp4' or unset")
-    if mode == "fp6":
-        model.quantize_decode_weights("fp6")
-        note("LWM_DECODE_WEIGHTS=fp6: projection kernels rounded in place to MXFP6 (e2m3) values; one-token steps stream the "
-             "6-bit packs")
-    if mode == "fp4":
-        model.quantize_decode_weights("fp4")
-        note("LWM_DECODE_WEIGHTS=fp4: projection kernels rounded in place to MXFP4 values; one-token steps of up to 4 rows stream "
-             "the 4-bit packs")
-    if mode == "fp8":
-        model.quantize_decode_weights("fp8")
-        note("LWM_DECODE_WEIGHTS=fp8: projection kernels rounded in place to e4m3 values; one-token steps stream the 8-bit packs")
+    if mode in FORMATS:
+        model.quantize_decode_weights(mode)
+        note(f"LWM_DECODE_WEIGHTS={mode}: {_DECODE_WEIGHTS_NOTES[mode]}")
     # LWM_DECODE_ROWS=N is read by the model itself (model.decode_rows) at every step: a bad value ends the run here, by name
     from ..llama_ops import parse_decode_rows
     try:

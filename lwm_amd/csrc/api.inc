@@ -871,6 +871,22 @@ static const ProjEntry kProjRowsW8 = {"gemm_rows_w8", "gemm_rows_w8", kRowsMax, 
                                       kRowsLdsBytes, 0};
 static const ProjEntry kProjRowsW6 = {"gemm_rows_w6", "gemm_rows_w6", kRowsMax, false, kRowsNT, true, true, false, true,
                                       kRowsLdsBytes, 0};
+
+// lwm_w8_quantise / lwm_w4_quantise / lwm_w6_quantise: the checks, the params, the grid and the launch.  P = the kernel's
+// params (w, q, scale, rounded, K, N); n_div = the columns one lane converts, nt = the columns of one workgroup.
+template <typename P, typename S>
+static int weight_quantise(const char* tag, int n_div, int nt, size_t lds_bytes, void (*kernel)(P), const void* w, void* q, S* scale,
+                           void* rounded, int32_t K, int32_t N, void* stream) {
+    if (!w || !q || !scale || !rounded) return fail(LWM_EINVAL, "%s: null pointer", tag);
+    if (K <= 0 || N <= 0) return fail(LWM_EINVAL, "%s: bad dimension", tag);
+    if ((K & 31) || K > 8 * 12 * kGemvKT || (N % n_div))
+        return fail(LWM_EUNSUPPORTED, "%s: K=%ld N=%ld (need K %% 32 == 0, K <= 12288, N %% 8 == 0)", tag, K, N);
+    if (!aligned16(w) || !aligned16(q) || !aligned16(scale) || !aligned16(rounded)) return fail(LWM_EINVAL, "%s: misaligned pointer", tag);
+    P p;
+    p.w = (const bf16_t*)w; p.q = (uint8_t*)q; p.scale = scale; p.rounded = (bf16_t*)rounded; p.K = K; p.N = N;
+    const long grid = (long)((K + kGemvKT - 1) / kGemvKT) * ((N + nt - 1) / nt);
+    return launch(tag, kernel, grid, 256, lds_bytes, stream, p);
+}
 }  // namespace lwm
 extern "C" {
 
@@ -901,49 +917,19 @@ int lwm_gemv_bf16(const void* x, int64_t ldx, const void* w, void* y, int64_t ld
 }
 
 int lwm_w8_quantise(const void* w, void* q, float* scale, void* rounded, int32_t K, int32_t N, void* stream) {
-    using namespace lwm;
-    if (!w || !q || !scale || !rounded) return fail(LWM_EINVAL, "%s", "w8_quantise: null pointer");
-    if (K <= 0 || N <= 0) return fail(LWM_EINVAL, "%s", "w8_quantise: bad dimension");
-    if ((K & 31) || K > 8 * 12 * kGemvKT || (N % kGemvW8CPL))
-        return fail(LWM_EUNSUPPORTED, "%s: K=%ld N=%ld (need K %% 32 == 0, K <= 12288, N %% 8 == 0)", "w8_quantise", K, N);
-    if (!aligned16(w) || !aligned16(q) || !aligned16(scale) || !aligned16(rounded))
-        return fail(LWM_EINVAL, "%s", "w8_quantise: misaligned pointer");
-    W8QuantParams p;
-    p.w = (const bf16_t*)w; p.q = (uint8_t*)q; p.scale = scale; p.rounded = (bf16_t*)rounded; p.K = K; p.N = N;
-    const long grid = (long)((K + kGemvKT - 1) / kGemvKT) * ((N + kW8QuantNT - 1) / kW8QuantNT);
-    return launch("w8_quantise", w8_quantise_kernel, grid, 256, 4 * 64 * 32, stream, p);
+    return lwm::weight_quantise("w8_quantise", lwm::kGemvW8CPL, lwm::kW8QuantNT, 4 * 64 * 32, lwm::w8_quantise_kernel, w, q, scale, rounded, K, N, stream);
 }
 
 int lwm_gemv_fused_w8(const LwmGemvW8Args* a, void* stream) { return lwm::proj_run(lwm::kProjGemvW8, lwm::gemv_w8_kernel, a, stream); }
 
 int lwm_w4_quantise(const void* w, void* q, void* scale_e8m0, void* rounded, int32_t K, int32_t N, void* stream) {
-    using namespace lwm;
-    if (!w || !q || !scale_e8m0 || !rounded) return fail(LWM_EINVAL, "%s", "w4_quantise: null pointer");
-    if (K <= 0 || N <= 0) return fail(LWM_EINVAL, "%s", "w4_quantise: bad dimension");
-    if ((K & 31) || K > 8 * 12 * kGemvKT || (N & 7))
-        return fail(LWM_EUNSUPPORTED, "%s: K=%ld N=%ld (need K %% 32 == 0, K <= 12288, N %% 8 == 0)", "w4_quantise", K, N);
-    if (!aligned16(w) || !aligned16(q) || !aligned16(scale_e8m0) || !aligned16(rounded))
-        return fail(LWM_EINVAL, "%s", "w4_quantise: misaligned pointer");
-    W4QuantParams p;
-    p.w = (const bf16_t*)w; p.q = (uint8_t*)q; p.scale = (uint8_t*)scale_e8m0; p.rounded = (bf16_t*)rounded; p.K = K; p.N = N;
-    const long grid = (long)((K + kGemvKT - 1) / kGemvKT) * ((N + kW4QuantNT - 1) / kW4QuantNT);
-    return launch("w4_quantise", w4_quantise_kernel, grid, 256, 0, stream, p);
+    return lwm::weight_quantise("w4_quantise", 8, lwm::kW4QuantNT, 0, lwm::w4_quantise_kernel, w, q, (uint8_t*)scale_e8m0, rounded, K, N, stream);
 }
 
 int lwm_gemv_fused_w4(const LwmGemvW4Args* a, void* stream) { return lwm::proj_run(lwm::kProjGemvW4, lwm::gemv_w4_kernel, a, stream); }
 
 int lwm_w6_quantise(const void* w, void* q, void* scale_e8m0, void* rounded, int32_t K, int32_t N, void* stream) {
-    using namespace lwm;
-    if (!w || !q || !scale_e8m0 || !rounded) return fail(LWM_EINVAL, "%s", "w6_quantise: null pointer");
-    if (K <= 0 || N <= 0) return fail(LWM_EINVAL, "%s", "w6_quantise: bad dimension");
-    if ((K & 31) || K > 8 * 12 * kGemvKT || (N & 7))
-        return fail(LWM_EUNSUPPORTED, "%s: K=%ld N=%ld (need K %% 32 == 0, K <= 12288, N %% 8 == 0)", "w6_quantise", K, N);
-    if (!aligned16(w) || !aligned16(q) || !aligned16(scale_e8m0) || !aligned16(rounded))
-        return fail(LWM_EINVAL, "%s", "w6_quantise: misaligned pointer");
-    W6QuantParams p;
-    p.w = (const bf16_t*)w; p.q = (uint8_t*)q; p.scale = (uint8_t*)scale_e8m0; p.rounded = (bf16_t*)rounded; p.K = K; p.N = N;
-    const long grid = (long)((K + kGemvKT - 1) / kGemvKT) * ((N + kW4QuantNT - 1) / kW4QuantNT);
-    return launch("w6_quantise", w6_quantise_kernel, grid, 256, 0, stream, p);
+    return lwm::weight_quantise("w6_quantise", 8, lwm::kW4QuantNT, 0, lwm::w6_quantise_kernel, w, q, (uint8_t*)scale_e8m0, rounded, K, N, stream);
 }
 
 int lwm_gemv_fused_w6(const LwmGemvW6Args* a, void* stream) { return lwm::proj_run(lwm::kProjGemvW6, lwm::gemv_w6_kernel, a, stream); }

@@ -81,22 +81,37 @@ struct GemvW4Format {
 // dynamic LDS: 3 * R * kGemvNT * 4 bytes (the host sizes it by the row count)
 LWM_KERNEL(kGemvThreads) void gemv_w4_kernel(GemvW4Params p) { gemv_by_rows<GemvW4Format>(p); }
 
-// ------------------------------------------------------------------ quantiser
-struct W4QuantParams {
+// ------------------------------------------------------------------ quantiser (the 4-bit and the 6-bit one: gemv_w6.h)
+struct MxQuantParams {
     const bf16_t* w;           // [K, N] bf16
-    uint8_t* q;                // [K/4, N/8, 16] e2m1 nibble pairs
+    uint8_t* q;                // [K/4, N/8, slot bytes] codes: 16 bytes of e2m1 nibble pairs, 24 bytes of e2m3 codes
     uint8_t* scale;            // [K/32, N] e8m0 bytes
-    bf16_t* rounded;           // [K, N] bf16(e2m1(q) * s); may be w itself
+    bf16_t* rounded;           // [K, N] bf16(code(q) * s); may be w itself
     int32_t K, N;              // K % 32 == 0, N % 8 == 0
 };
+typedef MxQuantParams W4QuantParams;
 
 constexpr int kW4QuantNT = 512;        // columns per workgroup: lane l owns columns 8l..8l+7 (one 16-byte load per row)
+
+// x = one row of the lane's 8 columns over its blocks' scales
+LWM_DEVICE void mx_quant_scaled(const u32x4& w, const float (&inv)[8], float (&x)[8]) {
+    unpack_bf16x8(w, x);
+    for (int c = 0; c < 8; ++c) x[c] *= inv[c];
+}
+
+// one row of `rounded`: the decoded codes of columns 2h, 2h + 1 in c[h], times the blocks' scales
+LWM_DEVICE void mx_quant_store_rounded(bf16_t* at, const f32x2& c0, const f32x2& c1, const f32x2& c2, const f32x2& c3, const float (&s)[8]) {
+    global_store_b128(at, u32x4{pack_bf16x2(c0[0] * s[0], c0[1] * s[1]), pack_bf16x2(c1[0] * s[2], c1[1] * s[3]),
+                                pack_bf16x2(c2[0] * s[4], c2[1] * s[5]), pack_bf16x2(c3[0] * s[6], c3[1] * s[7])});
+}
 
 // Workgroup = 128 rows of K x 512 columns; wave w holds rows 32w..32w+31 of its lanes' columns in registers (W is read
 // once).  Those 32 rows of a column are one MX block, so a lane has the whole block of each of its 8 columns: no LDS, no
 // shuffles.  K % 32 == 0: a wave's rows exist or do not as a whole.  Every thread loads all its rows before it stores any,
-// so `rounded` may be `w`.
-LWM_KERNEL(256) void w4_quantise_kernel(W4QuantParams p) {
+// so `rounded` may be `w`.  F: kExpDrop / kMantTop of the scale rule, offset() of a slot, and step(): four rows encoded,
+// their `rounded` rows written, their slot stored.
+template <typename F>
+LWM_DEVICE void mx_quantise_body(const MxQuantParams& p) {
     const int tid = thread_idx();
     const int wave = wave_uniform(tid >> 6), lane = tid & 63;
     const int nbn = (p.N + kW4QuantNT - 1) / kW4QuantNT;
@@ -119,14 +134,15 @@ LWM_KERNEL(256) void w4_quantise_kernel(W4QuantParams p) {
             am[2 * c] = lo > am[2 * c] ? lo : am[2 * c];
             am[2 * c + 1] = hi > am[2 * c + 1] ? hi : am[2 * c + 1];
         }
-    // amax = 1.m * 2^e: the smallest power of two s with amax / s <= 6 = 1.5 * 2^2 is 2^(e-2) when 1.m <= 1.5 and 2^(e-1)
-    // otherwise (Kv4Format's rule).  Biased exponent of s, clamped to 1 below; finite bf16 inputs stay under 254 by themselves.
+    // amax = 1.m * 2^e: the smallest power of two s with amax / s <= the format's largest code (6 = 1.5 * 2^2; 7.5 =
+    // 1.875 * 2^2) is 2^(e-2) when 1.m <= 1.5 (1.875) and 2^(e-1) otherwise (Kv4Format's / Kv6Format's rule).  Biased
+    // exponent of s, clamped to 1 below; finite bf16 inputs stay under 254 by themselves.
     float s[8], inv[8];
     uint32_t se8[8];
     for (int j = 0; j < 8; ++j) {
         int se = 127;
         if (am[j] != 0) {
-            se = (am[j] >> 7) - Kv4Format::kExpDrop + ((am[j] & 0x7f) > Kv4Format::kMantTop ? 1 : 0);
+            se = (am[j] >> 7) - F::kExpDrop + ((am[j] & 0x7f) > F::kMantTop ? 1 : 0);
             se = se < 1 ? 1 : se;
         }
         se8[j] = (uint32_t)se;
@@ -135,24 +151,31 @@ LWM_KERNEL(256) void w4_quantise_kernel(W4QuantParams p) {
     }
     global_store_b64(p.scale + (int64_t)(k0 / kGemvRPW) * p.N + n,
                      u32x2{se8[0] | se8[1] << 8 | se8[2] << 16 | se8[3] << 24, se8[4] | se8[5] << 8 | se8[6] << 16 | se8[7] << 24});
-    uint8_t* qp = p.q + GemvW4Format::offset(k0, n, p.N);
+    uint8_t* qp = p.q + F::offset(k0, n, p.N);
 #pragma unroll
-    for (int i0 = 0; i0 < kGemvRPW; i0 += 4) {
+    for (int i0 = 0; i0 < kGemvRPW; i0 += 4) F::step(wv, i0, inv, s, p.rounded + base, qp, p.N);
+}
+
+struct W4Quant {
+    static constexpr int kExpDrop = Kv4Format::kExpDrop, kMantTop = Kv4Format::kMantTop;
+    LWM_DEVICE static int64_t offset(int k, int n, int N) { return GemvW4Format::offset(k, n, N); }
+    // rows i0 .. i0 + 3 of the wave's 32: `rounded` at the first of the 32, qp at their first slot
+    LWM_DEVICE static void step(const u32x4 (&wv)[kGemvRPW], int i0, const float (&inv)[8], const float (&s)[8], bf16_t* rounded,
+                                uint8_t* qp, int N) {
         u32x4 slot;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float x[8];
-            unpack_bf16x8(wv[i0 + j], x);
-            for (int c = 0; c < 8; ++c) x[c] *= inv[c];
+            mx_quant_scaled(wv[i0 + j], inv, x);
             const uint32_t codes = Kv4Format::encode(x);
             slot[j] = codes;
-            const f32x2 c0 = cvt_e2m1x2<0>(codes), c1 = cvt_e2m1x2<1>(codes), c2 = cvt_e2m1x2<2>(codes), c3 = cvt_e2m1x2<3>(codes);
-            global_store_b128(p.rounded + base + (int64_t)(i0 + j) * p.N,
-                              u32x4{pack_bf16x2(c0[0] * s[0], c0[1] * s[1]), pack_bf16x2(c1[0] * s[2], c1[1] * s[3]),
-                                    pack_bf16x2(c2[0] * s[4], c2[1] * s[5]), pack_bf16x2(c3[0] * s[6], c3[1] * s[7])});
+            mx_quant_store_rounded(rounded + (int64_t)(i0 + j) * N, cvt_e2m1x2<0>(codes), cvt_e2m1x2<1>(codes), cvt_e2m1x2<2>(codes),
+                                   cvt_e2m1x2<3>(codes), s);
         }
-        global_store_b128(qp + (int64_t)(i0 >> 2) * p.N * 2, slot);
+        global_store_b128(qp + (int64_t)(i0 >> 2) * N * 2, slot);
     }
-}
+};
+
+LWM_KERNEL(256) void w4_quantise_kernel(W4QuantParams p) { mx_quantise_body<W4Quant>(p); }
 
 }  // namespace lwm

@@ -64,65 +64,19 @@ struct GemvW6Format : GemvW4Format {
 LWM_KERNEL(kGemvThreads) void gemv_w6_kernel(GemvW6Params p) { gemv_by_rows<GemvW6Format>(p); }
 
 // ------------------------------------------------------------------ quantiser
-struct W6QuantParams {
-    const bf16_t* w;           // [K, N] bf16
-    uint8_t* q;                // [K/4, N/8, 24] e2m3 codes
-    uint8_t* scale;            // [K/32, N] e8m0 bytes
-    bf16_t* rounded;           // [K, N] bf16(e2m3(q) * s); may be w itself
-    int32_t K, N;              // K % 32 == 0, N % 8 == 0
-};
+typedef MxQuantParams W6QuantParams;   // q: [K/4, N/8, 24] e2m3 codes
 
-// w4_quantise_kernel with the e2m3 encoder and the 24-byte slot.  Workgroup = 128 rows of K x 512 columns; wave w holds
-// rows 32w..32w+31 of its lanes' columns in registers, so a lane has the whole MX block of each of its 8 columns: no LDS, no
-// shuffles.  Every thread loads all its rows before it stores any, so `rounded` may be `w`.
-LWM_KERNEL(256) void w6_quantise_kernel(W6QuantParams p) {
-    const int tid = thread_idx();
-    const int wave = wave_uniform(tid >> 6), lane = tid & 63;
-    const int nbn = (p.N + kW4QuantNT - 1) / kW4QuantNT;
-    const int grp = block_idx_x() / nbn, nb = block_idx_x() % nbn;
-    const int k0 = grp * kGemvKT + wave * kGemvRPW;
-    const int n = nb * kW4QuantNT + lane * 8;
-    if (k0 >= p.K || n >= p.N) return;
-    const int64_t base = (int64_t)k0 * p.N + n;
-    u32x4 wv[kGemvRPW];
-#pragma unroll
-    for (int i = 0; i < kGemvRPW; ++i) wv[i] = global_load_b128(p.w + base + (int64_t)i * p.N);
-    // |w| as integers: bf16 magnitudes order like their bit patterns
-    int am[8];
-    for (int j = 0; j < 8; ++j) am[j] = 0;
-#pragma unroll
-    for (int i = 0; i < kGemvRPW; ++i)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const int lo = (int)(wv[i][c] & 0x7fffu), hi = (int)((wv[i][c] >> 16) & 0x7fffu);
-            am[2 * c] = lo > am[2 * c] ? lo : am[2 * c];
-            am[2 * c + 1] = hi > am[2 * c + 1] ? hi : am[2 * c + 1];
-        }
-    // amax = 1.m * 2^e: the smallest power of two s with amax / s <= 7.5 = 1.875 * 2^2 is 2^(e-2) when 1.m <= 1.875 and
-    // 2^(e-1) otherwise (Kv6Format's rule).  Biased exponent of s, clamped to 1 below; finite bf16 inputs stay under 254.
-    float s[8], inv[8];
-    uint32_t se8[8];
-    for (int j = 0; j < 8; ++j) {
-        int se = 127;
-        if (am[j] != 0) {
-            se = (am[j] >> 7) - Kv6Format::kExpDrop + ((am[j] & 0x7f) > Kv6Format::kMantTop ? 1 : 0);
-            se = se < 1 ? 1 : se;
-        }
-        se8[j] = (uint32_t)se;
-        s[j] = __builtin_bit_cast(float, (uint32_t)se << 23);
-        inv[j] = __builtin_bit_cast(float, (uint32_t)(254 - se) << 23);
-    }
-    global_store_b64(p.scale + (int64_t)(k0 / kGemvRPW) * p.N + n,
-                     u32x2{se8[0] | se8[1] << 8 | se8[2] << 16 | se8[3] << 24, se8[4] | se8[5] << 8 | se8[6] << 16 | se8[7] << 24});
-    uint8_t* qp = p.q + GemvW6Format::offset(k0, n, p.N);
-#pragma unroll
-    for (int i0 = 0; i0 < kGemvRPW; i0 += 4) {
+// mx_quantise_body (gemv_w4.h) with the e2m3 encoder and the 24-byte slot
+struct W6Quant {
+    static constexpr int kExpDrop = Kv6Format::kExpDrop, kMantTop = Kv6Format::kMantTop;
+    LWM_DEVICE static int64_t offset(int k, int n, int N) { return GemvW6Format::offset(k, n, N); }
+    LWM_DEVICE static void step(const u32x4 (&wv)[kGemvRPW], int i0, const float (&inv)[8], const float (&s)[8], bf16_t* rounded,
+                                uint8_t* qp, int N) {
         u32x2 h[4];                                // row j of the slot: 8 codes = 48 bits (32 + 16)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float x[8];
-            unpack_bf16x8(wv[i0 + j], x);
-            for (int c = 0; c < 8; ++c) x[c] *= inv[c];
+            mx_quant_scaled(wv[i0 + j], inv, x);
             h[j] = Kv6Format::encode(x);
         }
         // the slot's 192 bits: row j at bits [48 j, 48 j + 48)
@@ -132,15 +86,14 @@ LWM_KERNEL(256) void w6_quantise_kernel(W6QuantParams p) {
         cvt_e2m3x32_f32(slot, c);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            global_store_b128(p.rounded + base + (int64_t)(i0 + j) * p.N,
-                              u32x4{pack_bf16x2(c[4 * j][0] * s[0], c[4 * j][1] * s[1]), pack_bf16x2(c[4 * j + 1][0] * s[2], c[4 * j + 1][1] * s[3]),
-                                    pack_bf16x2(c[4 * j + 2][0] * s[4], c[4 * j + 2][1] * s[5]),
-                                    pack_bf16x2(c[4 * j + 3][0] * s[6], c[4 * j + 3][1] * s[7])});
-        uint8_t* sp = qp + (int64_t)(i0 >> 2) * p.N * 3;
+            mx_quant_store_rounded(rounded + (int64_t)(i0 + j) * N, c[4 * j], c[4 * j + 1], c[4 * j + 2], c[4 * j + 3], s);
+        uint8_t* sp = qp + (int64_t)(i0 >> 2) * N * 3;
         global_store_b64(sp, u32x2{slot[0], slot[1]});
         global_store_b64(sp + 8, u32x2{slot[2], slot[3]});
         global_store_b64(sp + 16, u32x2{slot[4], slot[5]});
     }
-}
+};
+
+LWM_KERNEL(256) void w6_quantise_kernel(W6QuantParams p) { mx_quantise_body<W6Quant>(p); }
 
 }  // namespace lwm

@@ -1,6 +1,7 @@
 """LWM_DECODE_ROWS / model.decode_rows: one-token steps of 5..N batch rows through lwm_gemm_rows_fused_bf16 / _w8 /
 _w6 (csrc/gemm_rows.h; the 8-bit and 6-bit entries where the model holds such packs, w8.py / w6.py; 4-bit packs have no rows
-entry and take the bf16 one over the rounded parameters) instead of the library GEMMs.  Opt-in: the matrix pipe adds the products of a group of K in another
+entry -- the `proj.entries[1]` of their record in wpack.FORMATS is None -- and take the bf16 one over the rounded parameters)
+instead of the library GEMMs.  Opt-in: the matrix pipe adds the products of a group of K in another
 order than the library GEMM does, so the low bits of such a step change.  llama_ops re-exports everything here."""
 import os
 

@@ -22,6 +22,7 @@ from .llama_ops import (LLaMAMLP, RMSNorm, apply_rotary_emb, chunked_lm_head_los
                         rows_x_ok, swiglu)
 from .ringattention import (blockwise_feedforward, concatenate_to_cache, ringattention,
                             ringattention_inference, sp_layout_is_explicit, sp_positions, sp_size_rank)
+from .wpack import FORMATS
 
 # The model sizes of lwm/llama.py:33-130:
 # name: (hidden, intermediate, layers, heads, max_sequence_length, rms_norm_eps)
@@ -454,9 +455,7 @@ class LLaMAForCausalLM(torch.nn.Module):
         self.ln_f = RMSNorm(cfg.hidden_size, cfg.rms_norm_eps, dtype)
         self.lm_head = _dense(cfg.hidden_size, cfg.vocab_size, cfg.initializer_range, dtype)
         self._freqs = None
-        self._w8 = None            # quantize_decode_weights("fp8"): {parameter name: lwm_amd.w8.W8Kernel}
-        self._w4 = None            # quantize_decode_weights("fp4"): {parameter name: lwm_amd.w4.W4Kernel}; _w8 stays None
-        self._w6 = None            # quantize_decode_weights("fp6"): {parameter name: lwm_amd.w6.W6Kernel}; one kind at a time
+        self._decode_packs = None  # quantize_decode_weights: (wpack.WeightFormat, {parameter name: its pack}); one kind at a time
         self._decode_rows = None   # decode_rows: None = LWM_DECODE_ROWS
         self._remat_blocks = None  # remat_blocks: None = LWM_REMAT_BLOCK
 
@@ -579,7 +578,7 @@ class LLaMAForCausalLM(torch.nn.Module):
             norm._lwm_bf16 = hit
         return hit[1]
 
-    # ---- 8-bit decode weights (extension; include/lwm_hip.h "8-bit decode weights", lwm_amd/w8.py)
+    # ---- 8-bit, 6-bit and 4-bit decode weights (extension; include/lwm_hip.h "8-bit decode weights" ff., lwm_amd/wpack.py)
     def _decode_weight_params(self):
         """(name, parameter) of every kernel a cached one-token step streams through the GEMV"""
         for i, blk in enumerate(self.h):
@@ -590,93 +589,79 @@ class LLaMAForCausalLM(torch.nn.Module):
 
     @torch.no_grad()
     def quantize_decode_weights(self, mode="fp8"):
-        """mode="fp8": every projection kernel of the blocks and lm_head is ROUNDED IN PLACE to its e4m3-representable
-        values (per 128 rows of K and column one power-of-two scale) and an 8-bit pack of it is kept beside it.  After it
-        the model IS the rounded model: prefill, training ops, LWM_DECODE_FUSED=0, batches over 4 rows (over decode_rows, where
-        that is set) run as before on the rounded bf16 parameters, while the fused one-token step and the f32 logits of the
-        heads at those row counts stream the packs (lwm_gemv_fused_w8; lwm_gemm_rows_fused_w8 above 4 rows) -- bit for bit what the bf16 GEMV gives on the rounded parameters, from 0.516 of the bytes.
-        The bf16 parameters stay: the weights take 1.516x their memory.  A pack whose parameter changes afterwards is
-        refused at its next use (RuntimeError): quantise again.  mode="bf16" / None = drop_decode_weights().
-        mode="fp4": the same with 4-bit packs (include/lwm_hip.h "4-bit decode weights", lwm_amd/w4.py): the kernels are ROUNDED
-        IN PLACE to their MXFP4 values (e2m1 codes, one power-of-two scale per 32 rows of K and column) and the fused one-token
-        step and the heads' f32 logits at up to 4 rows stream the packs (lwm_gemv_fused_w4) -- bit for bit what the bf16 GEMV
-        gives on the rounded parameters, from 0.266 of the bytes; the weights take 1.266x their memory.  There is no 4-bit
-        body for more than 4 rows: where decode_rows is set, steps of 5.. rows run lwm_gemm_rows_fused_bf16 over the bf16
-        parameters -- those ARE the rounded model, so that route computes the same model and only saves no bytes.  4-bit
-        round-to-nearest moves a model's logits far more than the 8-bit packs do: check quality on the model in use.
-        mode="fp6": the same with 6-bit packs (include/lwm_hip.h "6-bit decode weights", lwm_amd/w6.py): the kernels are ROUNDED
-        IN PLACE to their MXFP6 values (e2m3 codes -- three mantissa bits, as e4m3 -- and one power-of-two scale per 32 rows of K
-        and column); the fused one-token step and the heads' f32 logits stream the packs, lwm_gemv_fused_w6 at up to 4 rows and
-        lwm_gemm_rows_fused_w6 at 5..decode_rows rows -- bit for bit what the bf16 entries give on the rounded parameters, from
-        0.391 of the bytes (0.757 of the 8-bit packs'); the weights take 1.391x their memory.
-        A later "fp8" replaces the 4-bit or 6-bit packs (rounding the already rounded kernels again) and the other way round;
-        only one kind of pack is held at a time.
-        bf16 models on one rank."""
+        """Every projection kernel of the blocks and lm_head is ROUNDED IN PLACE to the values the format of `mode` can hold
+        and a pack of it is kept beside it.  After it the model IS the rounded model: prefill, training ops,
+        LWM_DECODE_FUSED=0 and batches over the format's rows run as before on the rounded bf16 parameters, while the fused
+        one-token step and the f32 logits of the heads stream the packs -- bit for bit what the bf16 entries give on the
+        rounded parameters, from a fraction of the bytes.  The bf16 parameters stay: the weights take 1 + that fraction of
+        their memory.  A pack whose parameter changes afterwards is refused at its next use (RuntimeError): quantise again.
+        A later call with another mode replaces the packs (rounding the already rounded kernels again); only one kind of
+        pack is held at a time.  mode="bf16" / None = drop_decode_weights().  bf16 models on one rank.
+        "fp8" (lwm_amd/w8.py): e4m3 codes, one power-of-two scale per 128 rows of K and column; 0.516 of the bytes;
+            lwm_gemv_fused_w8 at up to 4 rows, lwm_gemm_rows_fused_w8 at 5..decode_rows rows.
+        "fp6" (lwm_amd/w6.py): MXFP6, e2m3 codes -- three mantissa bits, as e4m3 -- and one power-of-two scale per 32 rows of
+            K and column; 0.391 of the bytes (0.757 of the 8-bit packs'); lwm_gemv_fused_w6 at up to 4 rows,
+            lwm_gemm_rows_fused_w6 at 5..decode_rows rows.
+        "fp4" (lwm_amd/w4.py): MXFP4, e2m1 codes, one power-of-two scale per 32 rows of K and column; 0.266 of the bytes;
+            lwm_gemv_fused_w4 at up to 4 rows.  There is no 4-bit body for more rows: where decode_rows is set, steps of 5..
+            rows run lwm_gemm_rows_fused_bf16 over the bf16 parameters -- those ARE the rounded model, so that route
+            computes the same model and only saves no bytes.  4-bit round-to-nearest moves a model's logits far more than
+            the 8-bit packs do: check quality on the model in use."""
         if mode in (None, "bf16"):
             return self.drop_decode_weights()
-        if mode not in ("fp8", "fp6", "fp4"):
+        fmt = FORMATS.get(mode)
+        if fmt is None:
             raise ValueError(f"quantize_decode_weights({mode!r}): 'fp8', 'fp6', 'fp4', or 'bf16' / None (drop_decode_weights)")
-        bits = {"fp8": "8-bit", "fp6": "6-bit", "fp4": "4-bit"}[mode]
         if self.dtype != torch.bfloat16:
-            raise NotImplementedError(f"quantize_decode_weights({mode!r}) with a float32 model: the {bits} packs are made from bf16 "
+            raise NotImplementedError(f"quantize_decode_weights({mode!r}) with a float32 model: the {fmt.bits} packs are made from bf16 "
                                       "kernels and the GEMV that streams them takes bf16 activations (--dtype=bf16, or bf16 weights)")
         if sp_size_rank("sp")[0] > 1:
             raise NotImplementedError(f"quantize_decode_weights({mode!r}) with sp > 1: the fused one-token step runs on one rank "
                                       "(one rank, or bf16 decode weights)")
-        if mode == "fp8":
-            from .w8 import quantise_weight
-        elif mode == "fp6":
-            from .w6 import quantise_weight
-        else:
-            from .w4 import quantise_weight
+        quantise_weight = getattr(fmt.module, "quantise_weight")
         packs = {}
         for name, p in self._decode_weight_params():
             try:
                 packs[name] = quantise_weight(p)
             except ValueError as e:
                 raise ValueError(f"quantize_decode_weights({mode!r}): {name}: {e}") from None
-        self._w8, self._w6, self._w4 = (packs if mode == m else None for m in ("fp8", "fp6", "fp4"))
+        self._decode_packs = (fmt, packs)
         return self
 
     def drop_decode_weights(self):
         """Back to bf16 weight streaming.  The parameters stay as they are (rounded, if they were quantised)."""
-        self._w8 = self._w6 = self._w4 = None
+        self._decode_packs = None
         return self
 
-    def _w8_packs(self, names, kernels):
-        """the packs of `kernels`, each checked against its parameter as it is NOW"""
-        return [self._w8[n].check(k, n) for n, k in zip(names, kernels)]
+    def decode_packs(self, mode=None):
+        """{parameter name: pack} if the packs of `mode` ("fp8", "fp6", "fp4") are held, else None; without a mode: the held
+        (wpack.WeightFormat, packs), or None"""
+        held = getattr(self, "_decode_packs", None)
+        if mode is None or held is None:
+            return held
+        return held[1] if held[0].mode == mode else None
 
-    def _w4_packs(self, names, kernels):
-        """the same for the 4-bit packs"""
-        return [self._w4[n].check(k, n) for n, k in zip(names, kernels)]
-
-    def _w6_packs(self, names, kernels):
-        """the same for the 6-bit packs"""
-        return [self._w6[n].check(k, n) for n, k in zip(names, kernels)]
+    def _checked_packs(self, names, kernels):
+        """the held packs of `kernels`, each checked against its parameter as it is NOW"""
+        packs = self._decode_packs[1]
+        return [packs[n].check(k, n) for n, k in zip(names, kernels)]
 
     def _decode_layers_fused(self, x, fc, attention_mask, position_ids, cache):
         """The blocks of a cached one-token step (lwm/llama.py:704-744 with q_len = 1) with each RMSNorm folded into the
         x load of the projections that follow it and each residual add into the reduction of the projection before it:
         per layer 4 fewer launches of the ~19; same roundings as the separate kernels (rstd sums in another order)."""
-        from . import llama_ops, w8
+        from . import llama_ops
         B, _, d = x.shape
-        # <= 4 rows: the GEMV; above (decode_rows): the same launch pairs on the matrix pipe.  (Looked up at call time: both
-        # modules' entries can be wrapped.)
+        # <= 4 rows: the GEMV; above (decode_rows): the same launch pairs on the matrix pipe.  (Looked up at call time: the
+        # entries can be wrapped.)
         gemv_fused = llama_ops.gemv_fused if B <= 4 else llama_ops.gemm_rows_fused
-        if getattr(self, "_w8", None) is not None:         # the same launch pairs over the 8-bit packs (bit for bit on the rounded parameters)
-            fused_w8 = w8.gemv_fused_w8 if B <= 4 else w8.gemm_rows_fused_w8
+        held = getattr(self, "_decode_packs", None)
+        # the same launch pairs over the held packs (bit for bit on the rounded parameters); a format without a rows entry
+        # leaves more than 4 rows to the rounded bf16 parameters
+        if held is not None and (B <= 4 or held[0].proj.entries[1] is not None):
+            fused_packs = getattr(held[0].module, held[0].proj.fused[1 if B > 4 else 0])
             names = {id(p): n for n, p in self._decode_weight_params()}
-            gemv_fused = lambda x, ks, **kw: fused_w8(x, self._w8_packs([names[id(k)] for k in ks], ks), **kw)    # noqa: E731
-        elif getattr(self, "_w6", None) is not None:       # ... over the 6-bit packs, at every row count as the 8-bit ones
-            from . import w6
-            fused_w6 = w6.gemv_fused_w6 if B <= 4 else w6.gemm_rows_fused_w6
-            names = {id(p): n for n, p in self._decode_weight_params()}
-            gemv_fused = lambda x, ks, **kw: fused_w6(x, self._w6_packs([names[id(k)] for k in ks], ks), **kw)    # noqa: E731
-        elif getattr(self, "_w4", None) is not None and B <= 4:    # ... over the 4-bit packs (above 4 rows: the rounded bf16 parameters)
-            from . import w4
-            names = {id(p): n for n, p in self._decode_weight_params()}
-            gemv_fused = lambda x, ks, **kw: w4.gemv_fused_w4(x, self._w4_packs([names[id(k)] for k in ks], ks), **kw)    # noqa: E731
+            gemv_fused = lambda x, ks, **kw: fused_packs(x, self._checked_packs([names[id(k)] for k in ks], ks), **kw)    # noqa: E731
         H, D = self.cfg.num_attention_heads, d // self.cfg.num_attention_heads
         x2 = x.reshape(B, d)
         ss = torch.zeros(B, 32, dtype=torch.float32, device=x.device)
@@ -841,50 +826,6 @@ class LLaMAForCausalLM(torch.nn.Module):
         return chunked_lm_head_loss(h, self.lm_head, target_tokens, loss_masks, chunk, sp_sharded=sp_sharded)
 
 
-def w8_head_logits(model, h, head, kind="w8"):
-    """f32 logits of a head through its 8-bit pack (quantize_decode_weights), where the model has one for `head` and the
-    rows go through the GEMV (at most four, no autograd) or, up to decode_rows, the rows entry; None otherwise -- the caller
-    then runs `dense(h, head, torch.float32)` as before (a stand-in model without packs always gets None).  kind="w6": the
-    same over the 6-bit packs (w6_head_logits)"""
-    packs = getattr(model, "_" + kind, None)
-    if packs is None:
-        return None
-    same = lambda p: p is head or (p.data_ptr() == head.data_ptr() and p.shape == head.shape and p.stride() == head.stride())
-    name = next((n for n in packs if "." not in n and same(getattr(model, n))), None)
-    rows = h.numel() // h.shape[-1]
-    limit = max(4, model_decode_rows(model) or 4)
-    if name is None or rows > limit or not h.is_cuda or h.dtype != torch.bfloat16 or torch.is_grad_enabled():
-        return None
-    import importlib
-    mod = importlib.import_module("." + kind, __package__)          # (looked up at call time: the entries can be wrapped)
-    h2 = h.reshape(rows, h.shape[-1])
-    if rows > 4 and not rows_x_ok(h2):
-        h2 = h2.clone(memory_format=torch.contiguous_format)
-    fused = getattr(mod, "gemv_fused_" + kind if rows <= 4 else "gemm_rows_fused_" + kind)
-    (y,) = fused(h2, getattr(model, f"_{kind}_packs")((name,), (head,)), out_dtype=torch.float32)
-    return y.reshape(*h.shape[:-1], y.shape[-1])
-
-
-def w6_head_logits(model, h, head):
-    """w8_head_logits for the 6-bit packs: the GEMV at up to four rows, lwm_gemm_rows_fused_w6 up to decode_rows"""
-    return w8_head_logits(model, h, head, "w6")
-
-
-def w4_head_logits(model, h, head):
-    """w8_head_logits for the 4-bit packs: at most four rows (more rows take the bf16 head, the rounded parameter)"""
-    packs = getattr(model, "_w4", None)
-    if packs is None:
-        return None
-    same = lambda p: p is head or (p.data_ptr() == head.data_ptr() and p.shape == head.shape and p.stride() == head.stride())
-    name = next((n for n in packs if "." not in n and same(getattr(model, n))), None)
-    rows = h.numel() // h.shape[-1]
-    if name is None or rows > 4 or not h.is_cuda or h.dtype != torch.bfloat16 or torch.is_grad_enabled():
-        return None
-    from . import w4
-    (y,) = w4.gemv_fused_w4(h.reshape(rows, h.shape[-1]), model._w4_packs((name,), (head,)), out_dtype=torch.float32)
-    return y.reshape(*h.shape[:-1], y.shape[-1])
-
-
 def model_decode_rows(model):
     """model.decode_rows; LWM_DECODE_ROWS for a stand-in model without the attribute"""
     try:
@@ -894,15 +835,24 @@ def model_decode_rows(model):
 
 
 def head_logits(model, h, head):
-    """f32 logits of `head`: through its 8-bit, 6-bit or 4-bit pack where the model has one, else `dense(h, head, torch.float32)`
-    (the GEMV for <= 4 rows, lwm_gemm_rows_fused_bf16 up to model.decode_rows, the library beyond)"""
-    y = w8_head_logits(model, h, head)
-    if y is None:
-        y = w6_head_logits(model, h, head)
-    if y is None:
-        y = w4_head_logits(model, h, head)
-    if y is not None:
-        return y
+    """f32 logits of `head`: through its 8-bit, 6-bit or 4-bit pack (quantize_decode_weights) where the model holds one for
+    `head` and the rows go through the GEMV (at most four, no autograd) or, up to decode_rows, the format's rows entry; else
+    `dense(h, head, torch.float32)` (the GEMV for <= 4 rows, lwm_gemm_rows_fused_bf16 up to model.decode_rows, the library
+    beyond) -- a stand-in model without packs always gets that"""
+    held = getattr(model, "_decode_packs", None)
+    rows = h.numel() // h.shape[-1]
+    if held is not None and h.is_cuda and h.dtype == torch.bfloat16 and not torch.is_grad_enabled():
+        fmt, packs = held
+        same = lambda p: p is head or (p.data_ptr() == head.data_ptr() and p.shape == head.shape and p.stride() == head.stride())
+        name = next((n for n in packs if "." not in n and same(getattr(model, n))), None)
+        limit = 4 if fmt.proj.entries[1] is None else max(4, model_decode_rows(model) or 4)
+        if name is not None and rows <= limit:
+            h2 = h.reshape(rows, h.shape[-1])
+            if rows > 4 and not rows_x_ok(h2):
+                h2 = h2.clone(memory_format=torch.contiguous_format)
+            fused = getattr(fmt.module, fmt.proj.fused[1 if rows > 4 else 0])      # (looked up at call time: the entries can be wrapped)
+            (y,) = fused(h2, model._checked_packs((name,), (head,)), out_dtype=torch.float32)
+            return y.reshape(*h.shape[:-1], y.shape[-1])
     with decode_rows_scope(model_decode_rows(model)):
         return dense(h, head, torch.float32)
 

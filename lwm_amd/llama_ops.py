@@ -354,8 +354,8 @@ def _is_dev(t):
 
 
 class ProjFormat(typing.NamedTuple):
-    """What tells the weight formats apart in the front end of the weight-streaming projections: BF16 here, w8.W8, w6.W6 and
-    w4.W4 (entries[1] is None where a format has no lwm_gemm_rows_fused_* entry: the 4-bit packs)"""
+    """What tells the weight formats apart in the front end of the weight-streaming projections: BF16 here, and the
+    `proj` of each record of wpack.FORMATS (entries[1] is None where a format has no lwm_gemm_rows_fused_* entry: the 4-bit packs)"""
     args: type                  # the ctypes struct of the fused entries
     entries: tuple              # their names: (lwm_gemv_fused_*, lwm_gemm_rows_fused_*)
     who: str                    # opens the refusals of the operand checks ...

@@ -256,11 +256,11 @@ def test_generate_streams_the_packs_and_equals_the_rounded_bf16_model(monkeypatc
     mask3[0, :4] = 0
     mask3[2, :1] = 0                                               # left padding
     before = {n: p.detach().clone() for n, p in model._decode_weight_params()}
-    assert model.quantize_decode_weights("fp4") is model and model._w8 is None
+    assert model.quantize_decode_weights("fp4") is model and model.decode_packs("fp8") is None
     # the model IS the rounded model: every parameter equals what its pack stands for, and moved by at most a third of
     # its block's amax (codes at most 2 apart at the top of a scale that holds amax / s > 3)
     for n, p in model._decode_weight_params():
-        pk = model._w4[n]
+        pk = model.decode_packs("fp4")[n]
         assert torch.equal(p, w4.w4_dequant(pk.q, pk.scale, pk.shape)), n
         amax = before[n].float().abs().reshape(-1, 32, p.shape[1]).amax(1).repeat_interleave(32, 0)
         assert ((p.float() - before[n].float()).abs() <= amax / 3).all(), n
@@ -275,7 +275,7 @@ def test_generate_streams_the_packs_and_equals_the_rounded_bf16_model(monkeypatc
     got = [model.generate(**r, **kw) for r in routes]
     n_calls = len(calls)
     assert n_calls >= len(routes) * (6 + 2 * 4) and set(calls) == {1, 2, 3}       # heads and the four launch pairs per layer
-    assert model.drop_decode_weights() is model and model._w4 is None and model._w8 is None
+    assert model.drop_decode_weights() is model and model.decode_packs("fp4") is None and model.decode_packs("fp8") is None
     ref = [model.generate(**r, **kw) for r in routes]
     assert len(calls) == n_calls                                   # bf16 streaming again
     for r, (tg, lg), (tr, lr) in zip(routes, got, ref):
@@ -296,7 +296,7 @@ def test_generate_vision_with_cfg(monkeypatch):
     cfg = VideoLLaMAConfig(**CFG, vision_vocab_size=272, sample_mode="vision")
     model = _spread(VideoLLaMAForCausalLM(cfg).cuda())
     model.quantize_decode_weights("fp4")
-    assert "vision_head" in model._w4 and "lm_head" in model._w4
+    assert "vision_head" in model.decode_packs("fp4") and "lm_head" in model.decode_packs("fp4")
     ids = torch.randint(3, 272, (1, 7), device="cuda")
     ids = torch.cat([ids, torch.full_like(ids, 1)], 0)            # conditional + unconditional
     calls = _count_calls(monkeypatch, w4, "gemv_fused_w4")
@@ -344,32 +344,32 @@ def test_switching_between_the_formats(monkeypatch):
     c8, c4 = _count_calls(monkeypatch, w8, "gemv_fused_w8"), _count_calls(monkeypatch, w4, "gemv_fused_w4")
     kw = dict(max_new_tokens=3, return_logits=True)
     model.quantize_decode_weights("fp8")
-    assert model._w4 is None and len(model._w8) == 2 * 7 + 1
+    assert model.decode_packs("fp4") is None and len(model.decode_packs("fp8")) == 2 * 7 + 1
     model.generate(ids, **kw)
     n8 = len(c8)
     assert n8 > 0 and not c4
     model.quantize_decode_weights("fp4")
-    assert model._w8 is None and len(model._w4) == 2 * 7 + 1
+    assert model.decode_packs("fp8") is None and len(model.decode_packs("fp4")) == 2 * 7 + 1
     t4, l4 = model.generate(ids, **kw)
     n4 = len(c4)
     assert n4 > 0 and len(c8) == n8
     model.quantize_decode_weights("bf16")
-    assert model._w8 is None and model._w4 is None
+    assert model.decode_packs("fp8") is None and model.decode_packs("fp4") is None
     tb, lb = model.generate(ids, **kw)
     assert len(c4) == n4 and len(c8) == n8 and torch.equal(t4, tb) and torch.equal(l4, lb)
     model.quantize_decode_weights("fp4").quantize_decode_weights("fp8")           # and back: the 8-bit packs replace the 4-bit ones
-    assert model._w4 is None and model._w8 is not None
+    assert model.decode_packs("fp4") is None and model.decode_packs("fp8") is not None
     t8, l8 = model.generate(ids, **kw)
     assert len(c8) > n8 and len(c4) == n4
     with pytest.raises(ValueError, match="int4"):
         model.quantize_decode_weights("int4")
     model.drop_decode_weights()
     monkeypatch.setenv("LWM_DECODE_WEIGHTS", "FP4")
-    assert _common.apply_decode_weights(model) is model and len(model._w4) == 2 * 7 + 1 and model._w8 is None
+    assert _common.apply_decode_weights(model) is model and len(model.decode_packs("fp4")) == 2 * 7 + 1 and model.decode_packs("fp8") is None
     f32 = LLaMAForCausalLM(LLaMAConfig(**CFG), torch.float32).cuda()
     with pytest.raises(NotImplementedError, match="float32 model"):
         f32.quantize_decode_weights("fp4")
-    assert f32._w4 is None
+    assert f32.decode_packs("fp4") is None
 
 
 def test_a_five_row_step_takes_the_bf16_rows_kernel(monkeypatch):

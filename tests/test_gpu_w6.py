@@ -178,11 +178,11 @@ def test_generate_streams_the_packs_and_equals_the_rounded_bf16_model(monkeypatc
     mask3[0, :4] = 0
     mask3[2, :1] = 0                                               # left padding
     before = {n: p.detach().clone() for n, p in model._decode_weight_params()}
-    assert model.quantize_decode_weights("fp6") is model and model._w8 is None and model._w4 is None
+    assert model.quantize_decode_weights("fp6") is model and model.decode_packs("fp8") is None and model.decode_packs("fp4") is None
     # the model IS the rounded model: every parameter equals what its pack stands for, and moved by less than a fifteenth
     # of its block's amax (codes at most 0.5 apart at the top of a scale that holds amax / s > 3.75)
     for n, p in model._decode_weight_params():
-        pk = model._w6[n]
+        pk = model.decode_packs("fp6")[n]
         assert torch.equal(p, w6.w6_dequant(pk.q, pk.scale, pk.shape)), n
         amax = before[n].float().abs().reshape(-1, 32, p.shape[1]).amax(1).repeat_interleave(32, 0)
         assert ((p.float() - before[n].float()).abs() < amax / 15).all(), n
@@ -197,7 +197,7 @@ def test_generate_streams_the_packs_and_equals_the_rounded_bf16_model(monkeypatc
     n_calls = len(calls)
     assert n_calls >= len(routes) * (6 + 2 * 4) and set(calls) == {1, 2, 3}       # heads and the four launch pairs per layer
     assert not rows_calls and not any(others)
-    assert model.drop_decode_weights() is model and model._w6 is None and model._w8 is None and model._w4 is None
+    assert model.drop_decode_weights() is model and model.decode_packs("fp6") is None and model.decode_packs("fp8") is None and model.decode_packs("fp4") is None
     ref = [model.generate(**r, **kw) for r in routes]
     assert len(calls) == n_calls                                   # bf16 streaming again
     for r, (tg, lg), (tr, lr) in zip(routes, got, ref):
@@ -218,7 +218,7 @@ def test_generate_vision_heads_stream_the_packs(monkeypatch):
     cfg = VideoLLaMAConfig(**CFG, vision_vocab_size=272, sample_mode="vision")
     model = _spread(VideoLLaMAForCausalLM(cfg).cuda())
     model.quantize_decode_weights("fp6")
-    assert "vision_head" in model._w6 and "lm_head" in model._w6
+    assert "vision_head" in model.decode_packs("fp6") and "lm_head" in model.decode_packs("fp6")
     ids = torch.randint(3, 272, (1, 7), device="cuda")
     ids = torch.cat([ids, torch.full_like(ids, 1)], 0)            # conditional + unconditional
     calls, others = _count_calls(monkeypatch, w6, "gemv_fused_w6"), _others(monkeypatch)
@@ -266,37 +266,37 @@ def test_switching_between_the_formats(monkeypatch):
     c8, c6, c4 = (_count_calls(monkeypatch, m, n) for m, n in ((w8, "gemv_fused_w8"), (w6, "gemv_fused_w6"), (w4, "gemv_fused_w4")))
     kw = dict(max_new_tokens=3, return_logits=True)
     model.quantize_decode_weights("fp6")
-    assert model._w8 is None and model._w4 is None and len(model._w6) == 2 * 7 + 1
+    assert model.decode_packs("fp8") is None and model.decode_packs("fp4") is None and len(model.decode_packs("fp6")) == 2 * 7 + 1
     t6, l6 = model.generate(ids, **kw)
     n6 = len(c6)
     assert n6 > 0 and not c8 and not c4
     model.quantize_decode_weights("fp8")
-    assert model._w6 is None and model._w4 is None and len(model._w8) == 2 * 7 + 1
+    assert model.decode_packs("fp6") is None and model.decode_packs("fp4") is None and len(model.decode_packs("fp8")) == 2 * 7 + 1
     model.generate(ids, **kw)
     n8 = len(c8)
     assert n8 > 0 and len(c6) == n6
     model.quantize_decode_weights("fp6")
-    assert model._w8 is None and len(model._w6) == 2 * 7 + 1
+    assert model.decode_packs("fp8") is None and len(model.decode_packs("fp6")) == 2 * 7 + 1
     model.generate(ids, **kw)
     assert len(c6) > n6 and len(c8) == n8
     n6 = len(c6)
     model.quantize_decode_weights("fp4")
-    assert model._w6 is None and model._w8 is None and len(model._w4) == 2 * 7 + 1
+    assert model.decode_packs("fp6") is None and model.decode_packs("fp8") is None and len(model.decode_packs("fp4")) == 2 * 7 + 1
     model.generate(ids, **kw)
     assert len(c4) > 0 and len(c6) == n6
     model.quantize_decode_weights("fp6").quantize_decode_weights("bf16")
-    assert model._w8 is None and model._w6 is None and model._w4 is None
+    assert model.decode_packs("fp8") is None and model.decode_packs("fp6") is None and model.decode_packs("fp4") is None
     n4 = len(c4)
     model.generate(ids, **kw)
     assert len(c6) == n6 and len(c8) == n8 and len(c4) == n4
     with pytest.raises(ValueError, match="int6"):
         model.quantize_decode_weights("int6")
     monkeypatch.setenv("LWM_DECODE_WEIGHTS", "FP6")
-    assert _common.apply_decode_weights(model) is model and len(model._w6) == 2 * 7 + 1 and model._w8 is None and model._w4 is None
+    assert _common.apply_decode_weights(model) is model and len(model.decode_packs("fp6")) == 2 * 7 + 1 and model.decode_packs("fp8") is None and model.decode_packs("fp4") is None
     f32 = LLaMAForCausalLM(LLaMAConfig(**CFG), torch.float32).cuda()
     with pytest.raises(NotImplementedError, match=r"'fp6'.*float32 model.*6-bit"):
         f32.quantize_decode_weights("fp6")
-    assert f32._w6 is None
+    assert f32.decode_packs("fp6") is None
 
 
 def test_a_five_row_step_takes_the_6_bit_rows_kernel(monkeypatch):

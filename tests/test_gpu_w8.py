@@ -254,7 +254,7 @@ def test_generate_streams_the_packs_and_equals_the_rounded_bf16_model(monkeypatc
     assert model.quantize_decode_weights("fp8") is model
     # the model IS the rounded model: every parameter equals what its pack stands for, and moved by at most 2^-4 of itself
     for n, p in model._decode_weight_params():
-        pk = model._w8[n]
+        pk = model.decode_packs("fp8")[n]
         K = p.shape[0]
         deq = pk.q.view(torch.float8_e4m3fn).float() * pk.scale.repeat_interleave(128, 0)[:K]
         assert torch.equal(p.float(), deq), n
@@ -269,7 +269,7 @@ def test_generate_streams_the_packs_and_equals_the_rounded_bf16_model(monkeypatc
     got = [model.generate(**r, **kw) for r in routes]
     n_calls = len(calls)
     assert n_calls >= len(routes) * (6 + 2 * 4) and set(calls) == {1, 2, 3}       # heads and the four launch pairs per layer
-    assert model.drop_decode_weights() is model and model._w8 is None
+    assert model.drop_decode_weights() is model and model.decode_packs("fp8") is None
     ref = [model.generate(**r, **kw) for r in routes]
     assert len(calls) == n_calls                                   # bf16 streaming again
     for r, (tg, lg), (tr, lr) in zip(routes, got, ref):
@@ -289,7 +289,7 @@ def test_generate_vision_with_cfg(monkeypatch):
     cfg = VideoLLaMAConfig(**CFG, vision_vocab_size=272, sample_mode="vision")
     model = _spread(VideoLLaMAForCausalLM(cfg).cuda())
     model.quantize_decode_weights("fp8")
-    assert "vision_head" in model._w8 and "lm_head" in model._w8
+    assert "vision_head" in model.decode_packs("fp8") and "lm_head" in model.decode_packs("fp8")
     ids = torch.randint(3, 272, (1, 7), device="cuda")
     ids = torch.cat([ids, torch.full_like(ids, 1)], 0)            # conditional + unconditional
     calls = _count_w8_calls(monkeypatch)
@@ -332,11 +332,11 @@ def test_refused_cases_are_named(monkeypatch):
     f32 = LLaMAForCausalLM(LLaMAConfig(**CFG), torch.float32).cuda()
     with pytest.raises(NotImplementedError, match="float32 model"):
         f32.quantize_decode_weights("fp8")
-    assert f32._w8 is None
+    assert f32.decode_packs("fp8") is None
     model = LLaMAForCausalLM(LLaMAConfig(**CFG)).cuda()
     monkeypatch.setenv("LWM_DECODE_WEIGHTS", "bogus")
     with pytest.raises(SystemExit, match="LWM_DECODE_WEIGHTS='bogus': 'fp8', 'bf16'"):
         _common.apply_decode_weights(model)
-    assert model._w8 is None
+    assert model.decode_packs("fp8") is None
     monkeypatch.setenv("LWM_DECODE_WEIGHTS", "fp8")
-    assert _common.apply_decode_weights(model) is model and len(model._w8) == 2 * 7 + 1
+    assert _common.apply_decode_weights(model) is model and len(model.decode_packs("fp8")) == 2 * 7 + 1

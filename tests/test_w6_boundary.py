@@ -230,7 +230,7 @@ def test_model_refusals_by_name():
         with pytest.raises(ValueError, match=r"'fp6'.*h\.0\.attention\.wq"):       # host parameters: no CPU path, named
             m.quantize_decode_weights("fp6")
         assert wire.reached == []
-    assert m._w6 is None and m._w8 is None and m.quantize_decode_weights("bf16") is m and m.drop_decode_weights() is m
+    assert m.decode_packs("fp6") is None and m.decode_packs("fp8") is None and m.quantize_decode_weights("bf16") is m and m.drop_decode_weights() is m
 
 
 def test_sp_ring_is_refused_by_name(monkeypatch):
@@ -239,7 +239,7 @@ def test_sp_ring_is_refused_by_name(monkeypatch):
     monkeypatch.setattr(llama, "sp_size_rank", lambda axis: (2, 0))
     with pytest.raises(NotImplementedError, match=r"'fp6'.*sp > 1"):
         m.quantize_decode_weights("fp6")
-    assert m._w6 is None
+    assert m.decode_packs("fp6") is None
 
 
 # ---------------------------------------------------------------- the entry points' environment switch

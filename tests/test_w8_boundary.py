@@ -213,7 +213,7 @@ def test_model_refusals_by_name():
         with pytest.raises(ValueError, match=r"h\.0\.attention\.wq"):       # host parameters: no CPU path, named
             m.quantize_decode_weights("fp8")
         assert wire.reached == []
-    assert m._w8 is None and m.quantize_decode_weights("bf16") is m and m.drop_decode_weights() is m
+    assert m.decode_packs("fp8") is None and m.quantize_decode_weights("bf16") is m and m.drop_decode_weights() is m
 
 
 def test_sp_ring_is_refused_by_name(monkeypatch):
